@@ -14,15 +14,22 @@ counter sums cross ranks.
 The timed region is K back-to-back launches (no events inside), issued
 round-robin on `--streams` HIP streams (default 2; the steps are independent
 passes, each with its own output buffers, so one launch's ragged end overlaps
-the next one's start); the serial single-stream loop is timed too and
-reported as `value_serial`.  Step k runs on resident batch k mod
+the next one's start).  Step k runs on resident batch k mod
 `--fresh-batches` (8 distinct batches of the same distribution, all resident
 before timing), so no launch replays the previous one's Infinity-Cache-warm
-rows; the one-batch replay rates are reported under `replay`.  A further pass
-of K launches bracketed by HIP events on one stream gives the kernel's own
-duration for the roofline.
+rows.  A plain run does only that: set up (which ends with 0.2 s of untimed
+launches that bring the GPU to its clocks), `--warmup` steps, the K timed
+steps, the result line (`value`, `ms_per_step` and the batch's counters).
+`--dump-outputs DIR` also writes what the last timed step computed (the
+PairResult of its batch) as DIR/<name>.npy; the inputs are Philox-keyed, so
+the same arguments give the same arrays from run to run and build to build.
 
-Extra fields: `roofline` for the validate kernel (algorithmic bytes per
+`--full` adds every other measurement to the line: the serial single-stream
+loop (`value_serial`), the one-batch replay rates (`replay`), and a further
+pass of K launches bracketed by HIP events on one stream, which gives the
+kernel's own duration for the roofline.
+
+Further `--full` fields: `roofline` for the validate kernel (algorithmic bytes per
 SURVEY §8(d): 144 B in + 76 B out + 32 B x (G + V) per attempt, G/V = the
 executed getGroundHeight / isValidState calls reported by the kernel itself,
 over the HIP-event-timed kernel duration), `cpu_baseline` (the CPU
@@ -53,6 +60,7 @@ from global_body_planner_amd import workload as W  # noqa: E402
 HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E (MI355X_MICROARCH.md chip table)
 BYTES_IN, BYTES_OUT, BYTES_PER_LOOKUP = 144, 76, 32
 METRIC = "valid extend-attempts/sec + time-to-first-solution, 1024×1024 rough_terrain"
+SPINUP_SECONDS = 0.2     # a plain run's untimed launches ahead of --warmup (measure())
 
 
 def parse():
@@ -100,7 +108,18 @@ def parse():
                    help="HIP streams for config 2's launches (small launches: more overlap pays)")
     p.add_argument("--fresh-batches", type=int, default=8,
                    help="distinct resident batches the timed steps cycle through (1: replay one)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: the serial and one-batch "
+                        "replay rates, the kernel's own duration and roofline, the CPU baselines, "
+                        "time-to-first-solution, configs 2 and 5, the lookup and extend "
+                        "microbenchmarks (each still under its own option above)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed (valid, s_new, t_new, flags, "
+                        "counts of that step's batch) as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(data, s, a, d, seconds, threads=1):
@@ -308,14 +327,19 @@ def extend_micro(T, s, tgt, d, seed, launches=10):
 
 
 
-def measure(T, s, a, d, B, res, args, dev, world, streams=None, batches=None):
+def measure(T, s, a, d, B, res, args, dev, world, streams=None, batches=None, full=True,
+            keep_last=False):
     """The timed region of the contract: K launches back to back between a
     barrier + synchronize on both sides, issued round-robin on S HIP streams
-    (each with its own outputs), then the same K serially on one stream, then K
-    launches bracketed by HIP events on the launch stream (the kernel's own
-    duration for the roofline).  `batches` (a list of (s, a, d) resident
-    batches) makes the serial pass cycle through distinct inputs instead.
-    Returns (elapsed_streams, elapsed_serial, kernel_ms)."""
+    (each with its own outputs).  With `full`, the same K serially on one
+    stream before it, and after it K launches bracketed by HIP events on the
+    launch stream (the kernel's own duration for the roofline); without,
+    those two are None (S = 1: the serial pass is the headline) and
+    SPINUP_SECONDS of untimed launches stand in for the earlier passes.  `batches`
+    (a list of (s, a, d) resident batches) makes the steps cycle through
+    distinct inputs instead.  `keep_last`: a copy of the PairResult the last
+    step of the headline pass wrote, taken before any later pass reuses it.
+    Returns (elapsed_streams, elapsed_serial, kernel_ms, last)."""
     import ctypes
     VP = ctypes.c_void_p
     stream = torch.cuda.current_stream(dev)
@@ -350,9 +374,30 @@ def measure(T, s, a, d, B, res, args, dev, world, streams=None, batches=None):
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    elapsed_serial = timed(lambda k: launch(ins[k % len(ins)], optr0, sp))
-    elapsed = timed(lambda k: launch(ins[k % len(ins)], optr[k % S], strs[k % S].cuda_stream)) \
-        if S > 1 else elapsed_serial
+    def serial(k):
+        launch(ins[k % len(ins)], optr0, sp)
+
+    def overlapped(k):
+        launch(ins[k % len(ins)], optr[k % S], strs[k % S].cuda_stream)
+
+    if not full:
+        # part of set-up: the passes --full runs ahead of the headline also bring the
+        # GPU to its clocks and touch every batch; without them a short timed region
+        # (20 steps = 2 ms) would start on a GPU still ramping up and read ~5 % low
+        t0, k = time.perf_counter(), 0
+        while time.perf_counter() - t0 < SPINUP_SECONDS:
+            for _ in range(100):
+                (overlapped if S > 1 else serial)(k)
+                k += 1
+            torch.cuda.synchronize()
+    elapsed_serial = timed(serial) if full or S == 1 else None
+    elapsed = timed(overlapped) if S > 1 else elapsed_serial
+    last = None
+    if keep_last:  # step K - 1 wrote outs[(K - 1) mod S]
+        o = outs[(args.steps - 1) % S]
+        last = type(o)(*[t.clone() for t in (o.valid, o.s_new, o.t_new, o.flags, o.counts)])
+    if not full:
+        return elapsed, elapsed_serial, None, last
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
           for _ in range(args.steps)]
     for e0, e1 in ev:
@@ -361,7 +406,7 @@ def measure(T, s, a, d, B, res, args, dev, world, streams=None, batches=None):
         e1.record(stream)
     torch.cuda.synchronize()
     kern_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev]))
-    return elapsed, elapsed_serial, kern_ms
+    return elapsed, elapsed_serial, kern_ms, last
 
 
 def config2_line(args, dev):
@@ -382,8 +427,8 @@ def config2_line(args, dev):
     if args.fresh_batches > 1:
         batches2 = [(s2, a2, d2)] + [W.make_attempts(T2, B2, W.CONFIG_SEEDS[2], index_base=k * B2)[:3]
                                      for k in range(1, args.fresh_batches)]
-    el, el_serial, kms = measure(T2, s2, a2, d2, B2, r2, args, dev, 1, streams=args.config2_streams,
-                                 batches=batches2)
+    el, el_serial, kms, _ = measure(T2, s2, a2, d2, B2, r2, args, dev, 1,
+                                    streams=args.config2_streams, batches=batches2)
     byts = B2 * (BYTES_IN + BYTES_OUT) + BYTES_PER_LOOKUP * gv
     ach = byts / (kms * 1e-3) / 1e9
     out = {"workload": "config 2: synth-rough-256, 65,536-attempt batch, isValidStateActionPair"
@@ -476,26 +521,120 @@ def main():
     # same distribution cycled): no replay of Infinity-Cache-warm rows, as in a
     # planner whose iterations never repeat their inputs
     batches = None
-    if args.fresh_batches > 1:
+    fresh = args.fresh_batches > 1
+    if fresh:
         batches = [(s, a, d)] + [W.make_attempts(T, B, args.seed, index_base=base + k * world * B)[:3]
                                  for k in range(1, args.fresh_batches)]
     replay = None
-    if batches is not None:  # (measured first: it also brings the GPU to its clocks)
-        el_rp, el_rps, _ = measure(T, s, a, d, B, res, args, dev, world)
+    if fresh and args.full:  # (measured first: it also brings the GPU to its clocks)
+        el_rp, el_rps, _, _ = measure(T, s, a, d, B, res, args, dev, world)
         el_rp = sharding.reduce_run(el_rp, [0], dev)[0]
         el_rps = sharding.reduce_run(el_rps, [0], dev)[0]
         replay = {"value": round(B * world * args.steps / el_rp, 1),
                   "value_serial": round(B * world * args.steps / el_rps, 1),
                   "definition": "every step on the same resident batch (round 1's protocol)"}
-    elapsed, elapsed_serial, kern_ms = measure(T, s, a, d, B, res, args, dev, world, batches=batches)
-    elapsed_serial = sharding.reduce_run(elapsed_serial, [0], dev)[0]
+    elapsed, elapsed_serial, kern_ms, last = measure(T, s, a, d, B, res, args, dev, world,
+                                                     batches=batches, full=args.full,
+                                                     keep_last=bool(args.dump_outputs))
+    if elapsed_serial is not None:
+        elapsed_serial = sharding.reduce_run(elapsed_serial, [0], dev)[0]
     del batches
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
 
     elapsed, sums = sharding.reduce_run(elapsed, [B, n_valid, n_ood, n_frag, gv, probes], dev)
     sums = torch.tensor(sums, dtype=torch.float64)
     tot_attempts = float(sums[0].item()) * args.steps
     value = tot_attempts / elapsed
 
+    if rank == 0:
+        out = {
+            "metric": METRIC,
+            "value": round(value, 1),
+            "unit": "extend-attempts/s",
+            "n_gpus": world,
+            "dist_backend": backend,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "streams": max(1, args.streams),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic (SURVEY §8(d) synth-rough-1024, Philox-keyed attempts)",
+            "config": {
+                "workload": "config 3: synth-rough-1024, 262,144-attempt batch per GPU, "
+                            "isValidStateActionPair[Reverse] 50/50",
+                "terrain": args.terrain, "batch_per_gpu": B, "global_batch": int(sums[0].item()),
+                "seed": args.seed, "kernel": args.kernel, "waves": args.waves,
+                "adaptive": args.adaptive, "terrain_storage": ["auto", "f32", "f64"][T.info()["storage"]],
+                "parallelism": f"shard{world} (no collective on the data path)",
+            },
+            "valid_true_per_s": round(float(sums[1].item()) * args.steps / elapsed, 1),
+            "valid_fraction": float(sums[1].item()) / float(sums[0].item()),
+            "ood_fraction": float(sums[2].item()) / float(sums[0].item()),
+            "fragile": int(sums[3].item()),
+            "lookups_per_attempt": float(sums[4].item()) / float(sums[0].item()),
+            "probes_issued_per_attempt": float(sums[5].item()) / float(sums[0].item()),
+            "inputs": (f"fresh: step k runs on resident batch k mod {args.fresh_batches} "
+                       "(distinct batches of the same distribution)" if fresh else "one resident batch"),
+        }
+    if args.full:
+        more = full_report(args, data, T, s, a, d, tgt, B, bytes_per_launch, elapsed, elapsed_serial,
+                           kern_ms, tot_attempts, replay, rank, world, local, dev)
+        if rank == 0:
+            out.update(more)
+    if rank == 0:
+        line = json.dumps(out)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ROW_BYTES = 4 + 8 * 8 + 8 + 8 + 8 + 4   # valid, nonfinite f32; s_new 8 x f64; t_new / flags / counts f64
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: the PairResult of the last timed step as <name>.npy,
+    every value finite.  s_new / t_new rows that step did not assign (no
+    GBP_F_SNEW_SET / GBP_F_TNEW_SET in flags.npy) are 0, whatever an earlier
+    step left in the reused buffer; a NaN or infinity the step did assign is
+    written as 0 too and counted per row in nonfinite.npy.  The uint32 flag
+    and count words are exact in float64.  More rows than fit 64 MB: a fixed
+    seeded sample of them, in ascending order, with their indices as
+    rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    flags = res.flags.cpu().numpy().view(np.uint32)
+    arr = {"valid": res.valid.cpu().numpy().astype(np.float32),
+           "s_new": res.s_new.cpu().numpy().copy(),
+           "t_new": res.t_new.cpu().numpy().copy(),
+           "flags": flags.astype(np.float64),
+           "counts": res.counts.cpu().numpy().view(np.uint32).astype(np.float64)}
+    arr["s_new"][(flags & L.F_SNEW_SET) == 0] = 0.0
+    arr["t_new"][(flags & L.F_TNEW_SET) == 0] = 0.0
+    bad_s, bad_t = ~np.isfinite(arr["s_new"]), ~np.isfinite(arr["t_new"])
+    arr["nonfinite"] = (bad_s.sum(axis=1) + bad_t).astype(np.float32)
+    arr["s_new"][bad_s] = 0.0
+    arr["t_new"][bad_t] = 0.0
+    n, keep = flags.shape[0], DUMP_MAX_BYTES // (DUMP_ROW_BYTES + 8)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(20251018).choice(n, size=keep, replace=False))
+        arr = {k: v[rows] for k, v in arr.items()}
+        arr["rows"] = rows.astype(np.float64)
+    for k, v in arr.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def full_report(args, data, T, s, a, d, tgt, B, bytes_per_launch, elapsed, elapsed_serial, kern_ms,
+                tot_attempts, replay, rank, world, local, dev):
+    """--full: everything the line holds beside the headline (every rank runs
+    the planner legs; rank 0 returns the fields)."""
     ttfs = ttfs2 = ttfs1 = ttfs_near = None
     if args.ttfs_runs > 0:
         ttfs = time_to_first_solution(data, args.terrain, args.ttfs_runs, args.plan_max_time, args,
@@ -519,93 +658,57 @@ def main():
         if world == 1 and args.cpu_seconds > 0:
             config5["cpu_baseline"] = config5_cpu_baseline(config5)
 
-    if rank == 0:
-        achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
-        traffic = None
-        if args.traffic_json and os.path.exists(args.traffic_json):
-            try:
-                with open(args.traffic_json) as f:
-                    tj = json.load(f)
-                km = re.search(r"<[^,]+, (true|false), (\d+),", tj.get("kernel", ""))
-                if (tj.get("terrain") == args.terrain and tj.get("batch") == B and km
-                        and int(km.group(2)) == args.waves
-                        and (km.group(1) == "true") == bool(args.adaptive)):
-                    traffic = tj.get("hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
-        out = {
-            "metric": METRIC,
-            "value": round(value, 1),
-            "unit": "extend-attempts/s",
-            "n_gpus": world,
-            "dist_backend": backend,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "streams": max(1, args.streams),
-            "value_serial": round(tot_attempts / elapsed_serial, 1),
-            "ms_per_step_serial": round(elapsed_serial / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (SURVEY §8(d) synth-rough-1024, Philox-keyed attempts)",
-            "config": {
-                "workload": "config 3: synth-rough-1024, 262,144-attempt batch per GPU, "
-                            "isValidStateActionPair[Reverse] 50/50",
-                "terrain": args.terrain, "batch_per_gpu": B, "global_batch": int(sums[0].item()),
-                "seed": args.seed, "kernel": args.kernel, "waves": args.waves,
-                "adaptive": args.adaptive, "terrain_storage": ["auto", "f32", "f64"][T.info()["storage"]],
-                "parallelism": f"shard{world} (no collective on the data path)",
-            },
-            "valid_true_per_s": round(float(sums[1].item()) * args.steps / elapsed, 1),
-            "valid_fraction": float(sums[1].item()) / float(sums[0].item()),
-            "ood_fraction": float(sums[2].item()) / float(sums[0].item()),
-            "fragile": int(sums[3].item()),
-            "lookups_per_attempt": float(sums[4].item()) / float(sums[0].item()),
-            "probes_issued_per_attempt": float(sums[5].item()) / float(sums[0].item()),
-            "kernel_ms_per_launch": round(kern_ms, 4),
-            "roofline": {
-                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
-                "achieved_per_step_overlapped": round(
-                    bytes_per_launch / (elapsed / args.steps) / 1e9, 1),
-                "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                "kernel": "k_validate_persistent" if args.kernel == "persistent" else "k_validate_direct",
-                "algorithmic_bytes_per_launch": bytes_per_launch,
-            },
-            "inputs": (f"fresh: step k runs on resident batch k mod {args.fresh_batches} "
-                       "(distinct batches of the same distribution)" if replay else "one resident batch"),
-            "replay": replay,
-            "time_to_first_solution": ttfs,
-            "time_to_first_solution_before_wall": ttfs_near,
-            "time_to_first_solution_config2": ttfs2,
-            "time_to_first_solution_config1": ttfs1,
-            "config5": config5,
-        }
-        if args.lookup_micro:
-            out["terrain_lookup"] = terrain_lookup_micro(T, data, dev)
-            out["extend_batch"] = extend_micro(T, s, tgt, d, args.seed)
-            if ttfs and ttfs.get("planner_extends_per_s"):
-                out["planner_vs_extend_batch"] = round(
-                    ttfs["planner_extends_per_s"] / out["extend_batch"]["extends_per_s"], 4)
-        if args.config2 and world == 1:
-            out["config2"] = config2_line(args, dev)
-        if world == 1 and args.cpu_seconds > 0:
-            s_h, a_h, d_h = s.cpu().numpy(), a.cpu().numpy(), d.cpu().numpy()
-            out["cpu_baseline"] = cpu_baseline(data, s_h, a_h, d_h, args.cpu_seconds)
-            # all host cores the box gives this job (OMP_NUM_THREADS there), OpenMP
-            # over attempts (SURVEY §8(d) CPU baseline (ii))
-            nt = int(os.environ.get("OMP_NUM_THREADS") or os.cpu_count() or 1)
-            out["cpu_baseline_all_cores"] = cpu_baseline(data, s_h, a_h, d_h,
-                                                         min(args.cpu_seconds, 5.0), nt)
-        line = json.dumps(out)
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, "w") as f:
-                f.write(line + "\n")
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    if rank != 0:
+        return None
+    achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
+    traffic = None
+    if args.traffic_json and os.path.exists(args.traffic_json):
+        try:
+            with open(args.traffic_json) as f:
+                tj = json.load(f)
+            km = re.search(r"<[^,]+, (true|false), (\d+),", tj.get("kernel", ""))
+            if (tj.get("terrain") == args.terrain and tj.get("batch") == B and km
+                    and int(km.group(2)) == args.waves
+                    and (km.group(1) == "true") == bool(args.adaptive)):
+                traffic = tj.get("hbm_bytes_per_launch")
+        except Exception:
+            traffic = None
+    out = {
+        "value_serial": round(tot_attempts / elapsed_serial, 1),
+        "ms_per_step_serial": round(elapsed_serial / args.steps * 1e3, 4),
+        "kernel_ms_per_launch": round(kern_ms, 4),
+        "roofline": {
+            "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS,
+            "achieved_per_step_overlapped": round(
+                bytes_per_launch / (elapsed / args.steps) / 1e9, 1),
+            "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+            "kernel": "k_validate_persistent" if args.kernel == "persistent" else "k_validate_direct",
+            "algorithmic_bytes_per_launch": bytes_per_launch,
+        },
+        "replay": replay,
+        "time_to_first_solution": ttfs,
+        "time_to_first_solution_before_wall": ttfs_near,
+        "time_to_first_solution_config2": ttfs2,
+        "time_to_first_solution_config1": ttfs1,
+        "config5": config5,
+    }
+    if args.lookup_micro:
+        out["terrain_lookup"] = terrain_lookup_micro(T, data, dev)
+        out["extend_batch"] = extend_micro(T, s, tgt, d, args.seed)
+        if ttfs and ttfs.get("planner_extends_per_s"):
+            out["planner_vs_extend_batch"] = round(
+                ttfs["planner_extends_per_s"] / out["extend_batch"]["extends_per_s"], 4)
+    if args.config2 and world == 1:
+        out["config2"] = config2_line(args, dev)
+    if world == 1 and args.cpu_seconds > 0:
+        s_h, a_h, d_h = s.cpu().numpy(), a.cpu().numpy(), d.cpu().numpy()
+        out["cpu_baseline"] = cpu_baseline(data, s_h, a_h, d_h, args.cpu_seconds)
+        # all host cores this job may use (OMP_NUM_THREADS), OpenMP over attempts
+        # (SURVEY §8(d) CPU baseline (ii))
+        nt = int(os.environ.get("OMP_NUM_THREADS") or os.cpu_count() or 1)
+        out["cpu_baseline_all_cores"] = cpu_baseline(data, s_h, a_h, d_h,
+                                                     min(args.cpu_seconds, 5.0), nt)
+    return out
 
 
 if __name__ == "__main__":

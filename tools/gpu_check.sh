@@ -5,7 +5,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 PYTEST_ARGS=${PYTEST_ARGS:--m gpu -q -x tests}
-BENCH_ARGS=${BENCH_ARGS:---steps 10 --warmup 2 --cpu-seconds 10}
+BENCH_ARGS=${BENCH_ARGS:---full --steps 10 --warmup 2 --cpu-seconds 10}
 timeout -k 10 ${PYTEST_TIMEOUT:-900} python -m pytest $PYTEST_ARGS > gpurun_out/pytest_gpu.log 2>&1
 rc=$?
 echo "pytest rc=$rc"; tail -25 gpurun_out/pytest_gpu.log

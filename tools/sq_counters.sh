@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=${SQ_OUT:-gpurun_out/sq}
 mkdir -p $OUT
-ARGS=${SQ_ARGS:---steps 5 --warmup 1 --cpu-seconds 0 --ttfs-runs 0 --lookup-micro 0 --config2 0 --fresh-batches 0 --streams 1}
+ARGS=${SQ_ARGS:---full --steps 5 --warmup 1 --cpu-seconds 0 --ttfs-runs 0 --lookup-micro 0 --config2 0 --fresh-batches 0 --streams 1}
 timeout -k 10 60 rocprofv3 --list-avail > $OUT/list_avail.txt 2>&1 || echo "list-avail rc=$?"
 i=0
 for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" \
