@@ -25,6 +25,7 @@ STORAGE_AUTO, STORAGE_F32, STORAGE_F64 = 0, 1, 2
 OPT_KERNEL, OPT_BLOCK, OPT_WAVES, OPT_LDS_COORDS, OPT_HELPERS = 1, 2, 4, 5, 8
 OPT_AFFINE_COORDS, OPT_COORD_MODE, OPT_XCD_MAP, OPT_FAST_RCP, OPT_FRAGILE_EPS = 9, 10, 13, 14, 15
 OPT_NN_STATS = 18
+OPT_REFILL_WINDOW = 19
 PLAN_HALT_TARGETS, PLAN_HALT_EXTEND, PLAN_HALT_CONNECT = 1, 2, 4
 PLAN_HALT_STAR, PLAN_HALT_STAR_PAIRS = 8, 16
 KERNEL_DIRECT, KERNEL_PERSISTENT = 0, 1
@@ -33,7 +34,7 @@ EXPORTS = [
     "gbp_version", "gbp_status_string", "gbp_device_count", "gbp_device_alloc",
     "gbp_device_free", "gbp_memcpy_h2d", "gbp_memcpy_d2h", "gbp_stream_synchronize",
     "gbp_terrain_create", "gbp_terrain_destroy", "gbp_terrain_info",
-    "gbp_terrain_set_option", "gbp_terrain_get_option",
+    "gbp_terrain_set_option", "gbp_terrain_get_option", "gbp_validate_lds_plan",
     "gbp_height_batch_dev", "gbp_height_batch_host",
     "gbp_normal_batch_dev", "gbp_normal_batch_host",
     "gbp_valid_states_dev", "gbp_valid_states_host",
@@ -111,6 +112,7 @@ def load(path=None):
         "gbp_terrain_info": (I, [P, P, P, P, P, P]),
         "gbp_terrain_set_option": (I, [P, I, I64]),
         "gbp_terrain_get_option": (I, [P, I, P]),
+        "gbp_validate_lds_plan": (I, [I, I, I64, I64, SZ, P, P, P]),
         "gbp_height_batch_dev": (I, [P, I64, P, P, P, P, P]),
         "gbp_height_batch_host": (I, [P, I64, P, P, P, P]),
         "gbp_normal_batch_dev": (I, [P, I64, P, P, P, P]),

@@ -186,7 +186,7 @@ constexpr int SN_RING = 2 * 64;  // entries per wave: < 64 left + up to 64 queue
 struct XBox {
   int seq, ack, fin, n_idle;
   unsigned long long act;
-  int st[64];
+  int st[64], row[64];
   uint32_t vb[64], r0[64], r1[64];
   double t[64], ts[64];
 };
@@ -202,12 +202,99 @@ __device__ unsigned long long gbp_loop_prof[8192 * 12];
 #define LP_ADD(k, a, b)
 #endif
 
+// The refill's prefetch window: each wave owns 64 + pf
+// row slots.  A lane's attempt lives in the slot `row` of its wave; the pf
+// slots no lane holds form a queue (LDS, always full): its first `staged`
+// entries hold the attempts cur .. cur + staged - 1, loaded a step ahead by
+// LDS-direct loads that nothing waits for until the next refill, the rest are
+// free.  A refill hands the staged slots to the idle lanes in rank order (the
+// lane's old slot takes the queue entry's place: popping the head and pushing
+// the tail of a full queue meet in one cell), so no row is copied.
+// Built only with -DGBP_REFILL_WINDOW (A/B): measured slower than the direct
+// refill, which is the default: no window (pf = 0), every
+// refill loads its rows itself, dir issued with the rows.
+[[maybe_unused]] constexpr int PF_MAX = 32;
+
+// LDS bytes behind the coordinate vectors: rows, s_new rings, the window's queue
+inline size_t rows_bytes(int block, int pf) {
+  const size_t nwv = (size_t)(block / WAVE);
+  return sizeof(double) * SA_ROW * (size_t)(WAVE + pf) * nwv + sizeof(SnewRec) * SN_RING * nwv +
+         sizeof(int) * ((nwv * (size_t)pf + 1) & ~(size_t)1);
+}
+
+// one attempt row (S 64 B, A 80 B, dir in the 19th double's low word) from
+// global memory straight into the LDS row at `row` (wave-uniform): lanes
+// 0..35 one dword each, lane 36 the dir byte.  The loads are not in the
+// compiler's count: the consumer waits vmcnt(0) itself (loads return in
+// order, so the compiler's own counted waits only get stricter).
+__device__ __forceinline__ void row_to_lds(const double *S, const double *A, const uint8_t *dir,
+                                           unsigned int i, double *row, int lane) {
+  const unsigned int lds = __builtin_amdgcn_readfirstlane(
+      (unsigned int)(uintptr_t)(__attribute__((address_space(3))) void *)row);
+  const uint32_t *src = lane < 16 ? (const uint32_t *)(S + 8 * (size_t)i) + lane
+                                  : (const uint32_t *)(A + 10 * (size_t)i) + (lane - 16);
+  unsigned int keep;
+  if (lane < 36)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src), "s"(lds) : "memory");
+  if (dir && lane == 36)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                 "global_load_lds_ubyte %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(dir + i), "s"(lds) : "memory");
+}
+
 template <class ZT, bool ADAPTIVE, int W, int CM, bool ONE>
 __global__ __launch_bounds__(512, W) void k_validate_persistent(
     TerrainView<ZT> T0, int n, const double *__restrict__ S, const double *__restrict__ A,
     const uint8_t *__restrict__ dir, int dir_all, uint8_t *__restrict__ valid,
     double *__restrict__ s_new, double *__restrict__ t_new, uint32_t *__restrict__ flags,
-    uint32_t *__restrict__ counts, const int *__restrict__ n_dev, int helpers, int xcd_map) {
+    uint32_t *__restrict__ counts, const int *__restrict__ n_dev, int helpers, int xcd_map, int pf) {
+  if (n_dev) n = *n_dev;  // batch size produced on the device (planner loop)
+  const int lane = threadIdx.x & (WAVE - 1);
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  // (wave-uniform values the compiler cannot prove uniform: kept in scalar registers)
+  const int nwv = blockDim.x / WAVE, wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
+  double *const SA = gbp_smem + (CM == 1 ? (T0.nx + T0.ny + 1) & ~1 : 0);  // attempt rows
+  double *const wave_rows = SA + (size_t)wv * (WAVE + pf) * SA_ROW;
+  SnewRec *const ring = (SnewRec *)(SA + (size_t)nwv * (WAVE + pf) * SA_ROW) + wv * SN_RING;
+  [[maybe_unused]] int *const Q = (int *)(ring + (nwv - wv) * SN_RING) + wv * pf;  // the window's slot queue
+  // behind the queues: the A/B variants' regions (GBP_XWAVE, GBP_LDS_TERRAIN)
+  [[maybe_unused]] void *const lds_extra = Q + (((nwv * pf + 1) & ~1) - wv * pf);
+  // work source: a fixed contiguous slice [cur, end) per wave, handed out to
+  // the wave's idle lanes in order (no atomics).  Dynamic dequeues (one or
+  // eight device-scope heads, chunked, per-workgroup LDS queues; round 4: the
+  // last 15-60 % of a batch in chunks from 64 counters) were measured no
+  // faster (DESIGN.md section 5.1) and removed.
+  unsigned int cur, end;
+  {
+    const unsigned int waves = gridDim.x * (blockDim.x / WAVE);
+    // xcd_map: workgroup b runs on XCD b % 8 (round-robin dispatch); numbering
+    // the slices XCD-major gives each XCD one contiguous eighth of the batch,
+    // so a batch ordered by position keeps each XCD's L2 on its own stripe
+    const unsigned int wg = (xcd_map && (gridDim.x & 7u) == 0)
+                                ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3)
+                                : blockIdx.x;
+    const unsigned int wid = wg * (blockDim.x / WAVE) + wv;
+    cur = __builtin_amdgcn_readfirstlane((unsigned int)(((unsigned long long)n * wid) / waves));
+    end = __builtin_amdgcn_readfirstlane((unsigned int)(((unsigned long long)n * (wid + 1)) / waves));
+  }
+  // one attempt's row and direction into registers: dir is issued with the
+  // rows, so a refill that loads its rows itself waits one round trip, not two
+  auto load_row = [&](unsigned int i, double *r, int &d) {
+    if (dir) d = dir[i];
+#pragma unroll
+    for (int k = 0; k < 8; k++) r[k] = S[8 * (size_t)i + k];
+#pragma unroll
+    for (int k = 0; k < 10; k++) r[8 + k] = A[10 * (size_t)i + k];
+  };
+#ifdef GBP_REFILL_WINDOW
+  // the wave's first rows, fetched (cold) ahead of the coordinate staging
+  const unsigned int take0 = min(end - cur, (unsigned int)WAVE);
+  double row0[18];
+  int dir0 = dir_all;
+  if ((unsigned int)lane < take0) load_row(cur + lane, row0, dir0);
+#endif
 #ifndef GBP_LDS_TERRAIN
   const TerrainView<ZT> T = CM == 1 ? stage_coords(T0, gbp_smem) : T0;
 #else
@@ -216,9 +303,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   // terrains small enough: the host checks the fit), every gather from LDS
   TerrainView<ZT> T = CM == 1 ? stage_coords(T0, gbp_smem) : T0;
   {
-    ZT *zl = (ZT *)((SnewRec *)(gbp_smem + (CM == 1 ? (T0.nx + T0.ny + 1) & ~1 : 0) +
-                                (size_t)blockDim.x * SA_ROW) +
-                    (blockDim.x / WAVE) * SN_RING);
+    ZT *zl = (ZT *)lds_extra;
     const int nz = 2 * (T0.nx - 1) * T0.ny;  // ZT elements (even: 8-B aligned pairs)
     typedef ZT zpair __attribute__((ext_vector_type(2)));
     for (int i = threadIdx.x; i < nz / 2; i += blockDim.x)
@@ -229,12 +314,6 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
 #endif
   }
 #endif
-  if (n_dev) n = *n_dev;  // batch size produced on the device (planner loop)
-  const int lane = threadIdx.x & (WAVE - 1);
-  const unsigned long long lt_mask = (1ull << lane) - 1ull;
-  double *const SA = gbp_smem + (CM == 1 ? (T0.nx + T0.ny + 1) & ~1 : 0);  // attempt rows
-  double *const wave_rows = SA + (size_t)(threadIdx.x & ~(WAVE - 1)) * SA_ROW;
-  SnewRec *const ring = (SnewRec *)(SA + (size_t)blockDim.x * SA_ROW) + (threadIdx.x / WAVE) * SN_RING;
   int ring_n = 0;  // wave-uniform
   // s_new of the ring's first cnt entries, one per lane (converged)
   auto flush = [&](int cnt) {
@@ -256,12 +335,11 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     }
   };
 #ifdef GBP_XWAVE
-  XBox *const xbox = (XBox *)((SnewRec *)(SA + (size_t)blockDim.x * SA_ROW) + (blockDim.x / WAVE) * SN_RING);
-  const int wv = threadIdx.x / WAVE;
+  XBox *const xbox = (XBox *)lds_extra;
   XBox *const mybox = xbox + wv;
   XBox *const pbox = xbox + (wv ^ 1);
   const bool has_partner = (wv ^ 1) < (int)(blockDim.x / WAVE);
-  double *const partner_rows = SA + (size_t)((wv ^ 1) * WAVE) * SA_ROW;
+  double *const partner_rows = SA + (size_t)(wv ^ 1) * (WAVE + pf) * SA_ROW;
   if (lane == 0) {
     mybox->seq = 0;
     mybox->ack = 0;
@@ -272,27 +350,29 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   bool fin_sent = false;
 #endif
   Lane L;
-  L.s = SA + (size_t)threadIdx.x * SA_ROW;
+  int row = lane;  // this lane's row slot among its wave's 64 + pf
+  L.s = wave_rows + row * SA_ROW;
   L.a = L.s + 8;
   L.stage = ST_IDLE;
-  // work source: a fixed contiguous slice [cur, end) per wave, handed out to
-  // the wave's idle lanes in order (no atomics).  Dynamic dequeues (one or
-  // eight device-scope heads, chunked, per-workgroup LDS queues; round 4: the
-  // last 15-60 % of a batch in chunks from 64 counters) were measured no
-  // faster (DESIGN.md section 5.1) and removed.
-  unsigned int cur, end;
-  {
-    const unsigned int waves = gridDim.x * (blockDim.x / WAVE);
-    // xcd_map: workgroup b runs on XCD b % 8 (round-robin dispatch); numbering
-    // the slices XCD-major gives each XCD one contiguous eighth of the batch,
-    // so a batch ordered by position keeps each XCD's L2 on its own stripe
-    const unsigned int wg = (xcd_map && (gridDim.x & 7u) == 0)
-                                ? (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3)
-                                : blockIdx.x;
-    const unsigned int wid = wg * (blockDim.x / WAVE) + threadIdx.x / WAVE;
-    cur = (unsigned int)(((unsigned long long)n * wid) / waves);
-    end = (unsigned int)(((unsigned long long)n * (wid + 1)) / waves);
+  // a fresh attempt i of direction d in the lane's row
+  auto start = [&](unsigned int i, int d) {
+    L.idx = (int)i;
+    L.f = 0;
+    L.acc = Acc{0, 0, 0};
+    L.snew_kind = SN_NONE;
+    L.tnew_set = 0;
+    enter_stage(L, d == GBP_FORWARD ? ST_FWD_STANCE : ST_REV_FLIGHT);
+  };
+#ifdef GBP_REFILL_WINDOW
+  unsigned int staged = 0, qh = 0;  // the queue's staged entries and its head (wave-uniform)
+  if (lane < pf) Q[lane] = WAVE + lane;
+  if ((unsigned int)lane < take0) {
+#pragma unroll
+    for (int k = 0; k < 18; k++) L.s[k] = row0[k];
+    start(cur + lane, dir0);
   }
+  cur += take0;
+#endif
 #ifdef GBP_LOOP_PROF
   unsigned long long lp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   lp[8] = __builtin_amdgcn_s_memrealtime();
@@ -306,22 +386,51 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
       const unsigned int take = min(end - cur, (unsigned int)__popcll(m));
       const unsigned int rank = (unsigned int)__popcll(m & lt_mask);
       const bool mine = need && rank < take;
-      if (mine) {
-        const unsigned int i = cur + rank;
-        L.idx = (int)i;
+      unsigned int ts = 0;
+#ifdef GBP_REFILL_WINDOW
+      // the first `ts` of them from the window: a slot swap, no copy
+      ts = min(take, staged);
+      if (ts) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the window's loads, issued a step ago
+        if (mine && rank < ts) {
+          unsigned int p = qh + rank;
+          p -= p >= (unsigned int)pf ? (unsigned int)pf : 0u;
+          const int got = Q[p];
+          Q[p] = row;  // the slot given up is free window space
+          row = got;
+          L.s = wave_rows + row * SA_ROW;
+          L.a = L.s + 8;
+          start(cur + rank, dir ? ((const int *)L.s)[36] & 0xFF : dir_all);
+        }
+        qh += ts;
+        qh -= qh >= (unsigned int)pf ? (unsigned int)pf : 0u;
+        staged -= ts;
+      }
+#endif
+      if (mine && rank >= ts) {  // the rest, and every refill of a build without the window
+        double r[18];
+        int d = dir_all;
+        load_row(cur + rank, r, d);
 #pragma unroll
-        for (int k = 0; k < 8; k++) L.s[k] = S[8 * (size_t)i + k];
-#pragma unroll
-        for (int k = 0; k < 10; k++) L.a[k] = A[10 * (size_t)i + k];
-        L.f = 0;
-        L.acc = Acc{0, 0, 0};
-        L.snew_kind = SN_NONE;
-        L.tnew_set = 0;
-        const int d = dir ? dir[i] : dir_all;
-        enter_stage(L, d == GBP_FORWARD ? ST_FWD_STANCE : ST_REV_FLIGHT);
+        for (int k = 0; k < 18; k++) L.s[k] = r[k];
+        start(cur + rank, d);
       }
       cur += take;
     }
+#ifdef GBP_REFILL_WINDOW
+    // top the window up to the slice's next pf attempts: the loads land during
+    // this step's state check; nothing waits for them before the next refill
+    if (pf && min(end - cur, (unsigned int)pf) > staged) {
+      const unsigned int want = min(end - cur, (unsigned int)pf);
+      const int qv = Q[lane < pf ? lane : 0];
+      for (unsigned int k = staged; k < want; k++) {
+        unsigned int p = qh + k;
+        p -= p >= (unsigned int)pf ? (unsigned int)pf : 0u;
+        row_to_lds(S, A, dir, cur + k, wave_rows + __builtin_amdgcn_readlane(qv, p) * SA_ROW, lane);
+      }
+      staged = want;
+    }
+#endif
     const unsigned long long act = __ballot(L.stage != ST_IDLE);
 #ifdef GBP_XWAVE
     // this wave's work is done: serve the partner's requests until it is done
@@ -377,6 +486,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
                   __hip_atomic_load(&pbox->fin, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0;
       if (xhelp) {
         mybox->st[lane] = L.stage;
+        mybox->row[lane] = row;
         mybox->t[lane] = L.t;
         mybox->ts[lane] = L.ts;
         mybox->vb[lane] = L.acc.V;
@@ -396,7 +506,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
       const int j = pbox->n_idle + lane;
       const int src = nth_set_bit(pact, j % pn);
       slot = 1 + j / pn;
-      ps = partner_rows + src * SA_ROW;
+      ps = partner_rows + pbox->row[src] * SA_ROW;
       st = pbox->st[src];
       double t = pbox->t[src], ts = pbox->ts[src];
       vbase = pbox->vb[src];
@@ -410,7 +520,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
       const int j = __popcll(idle & lt_mask);
       const int src = owner ? lane : nth_set_bit(act, j % n_act);
       slot = owner ? 0 : 1 + j / n_act;
-      ps = wave_rows + src * SA_ROW;  // the owner's attempt row
+      ps = wave_rows + __shfl(row, src) * SA_ROW;  // the owner's attempt row
       st = __shfl(L.stage, src);
       double t = __shfl(L.t, src), ts = __shfl(L.ts, src);
       vbase = __shfl(L.acc.V, src);
@@ -980,6 +1090,33 @@ int validate_coord_mode(const gbp_terrain *t, bool direct) {
   return coord_mode(t, lds_ok);
 }
 
+// rows of the refill's prefetch window per wave (k_validate_persistent): as
+// many of PF_MAX as fit behind the coordinate vectors and the 64 rows, both in
+// a workgroup's limit and among the workgroups that share a CU's 160 KB; 0
+// (every refill loads its rows itself) when nothing fits.  The coordinate mode
+// is chosen first (validate_coord_mode) and never gives way to the window.
+// LDS of the A/B variants' own regions behind the rows (GBP_LDS_TERRAIN sizes its own)
+inline size_t variant_lds(const gbp_terrain *t) {
+#ifdef GBP_XWAVE
+  return sizeof(XBox) * (size_t)(t->opt_block / WAVE);  // the helper exchange's boxes
+#else
+  return 0;
+#endif
+}
+
+int refill_window(const gbp_terrain *t, size_t coords, size_t extra) {
+#if !defined(GBP_REFILL_WINDOW) || defined(GBP_LDS_TERRAIN)
+  return 0;  // the default build has no window
+#else
+  const int block = (int)t->opt_block;
+  const size_t wgs = (size_t)std::max<int64_t>(1, t->opt_waves * 256 / block);
+  const size_t cap = std::min<size_t>(t->lds_max, 160 * 1024 / wgs);
+  for (int pf = PF_MAX; pf > 0; pf--)
+    if (coords + rows_bytes(block, pf) + extra <= cap) return pf;
+  return 0;
+#endif
+}
+
 template <class ZT, bool AD, int W, int CM, bool ONE>
 int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *a,
                       const uint8_t *dir, int dir_all, uint8_t *valid, double *s_new,
@@ -988,7 +1125,6 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
   const TerrainView<ZT> T = view<ZT>(t);
   const int block = (int)t->opt_block;
   const size_t coords = CM == 1 ? stage_bytes(t->nx, t->ny) : 0;
-  const size_t rows = sizeof(double) * SA_ROW * (size_t)block;  // persistent kernel only
   const int64_t chunk = (int64_t)1 << 30;
   for (int64_t off = 0; off < n; off += chunk) {
     const int64_t m = std::min<int64_t>(n - off, chunk);
@@ -1014,19 +1150,16 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
       // waves starting with idle lanes that help from the first step
       // (65,536 attempts: 0.084 -> 0.072 ms; 262,144: unchanged)
       const int64_t g = std::max<int64_t>(1, std::min<int64_t>(resident, (m + WAVE - 1) / WAVE));
-      const size_t ring = sizeof(SnewRec) * SN_RING * (size_t)(block / WAVE);
 #ifdef GBP_LDS_TERRAIN
       const size_t zb = sizeof(ZT) * 2 * (size_t)(t->nx - 1) * t->ny;
-      if (coords + rows + ring + zb > t->lds_max) return GBP_E_SHAPE;  // the A/B variant only
-#elif defined(GBP_XWAVE)
-      const size_t zb = sizeof(XBox) * (size_t)(block / WAVE);  // the helper exchange's boxes
+      if (coords + rows_bytes(block, 0) + zb > t->lds_max) return GBP_E_SHAPE;  // the A/B variant only
 #else
-      const size_t zb = 0;
+      const size_t zb = variant_lds(t);
 #endif
+      const int pf = refill_window(t, coords, zb);
       hipLaunchKernelGGL((k_validate_persistent<ZT, AD, W, CM, ONE>), dim3((unsigned)g), dim3(block),
-                         coords + rows + ring + zb, st, T, (int)m, s + 8 * off, a + 10 * off, d, dir_all, v, sn, tn,
-                         flags + off, c, n_dev, (int)t->opt_helpers,
-                         (int)t->opt_xcd_map);
+                         coords + rows_bytes(block, pf) + zb, st, T, (int)m, s + 8 * off, a + 10 * off, d, dir_all,
+                         v, sn, tn, flags + off, c, n_dev, (int)t->opt_helpers, (int)t->opt_xcd_map, pf);
     }
     HIPCHK(hipGetLastError());
   }
@@ -1190,6 +1323,27 @@ int gbp_loop_prof_read(unsigned long long *out, int n_waves) {
   return GBP_OK;
 }
 #endif
+
+int gbp_validate_lds_plan(int nx, int ny, int64_t block, int64_t waves, size_t lds_max,
+                          int *coord_lds, int *window, size_t *bytes) {
+  if (nx < 2 || ny < 2 || block < WAVE || block > 512 || block % WAVE || waves < 1)
+    return GBP_E_INVALID_ARG;
+  gbp_terrain t;  // only the fields the sizing reads
+  t.nx = nx;
+  t.ny = ny;
+  t.one_x = t.one_y = 1;
+  t.opt_affine = 0;
+  t.opt_block = block;
+  t.opt_waves = waves;
+  t.lds_max = lds_max;
+  const int cm = validate_coord_mode(&t, false);
+  const size_t coords = cm == 1 ? stage_bytes(nx, ny) : 0;
+  const int pf = refill_window(&t, coords, variant_lds(&t));
+  if (coord_lds) *coord_lds = cm == 1;
+  if (window) *window = pf;
+  if (bytes) *bytes = coords + rows_bytes((int)block, pf) + variant_lds(&t);
+  return GBP_OK;
+}
 
 int gbp_version(void) { return 200; /* 0.2.0: extend flags, FRAGILE re-decision, trees */ }
 
@@ -1436,6 +1590,10 @@ int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value) {
     case GBP_OPT_FRAGILE_EPS: *value = (int64_t)std::llround(t->fragile_eps * 1e15); return GBP_OK;
     case GBP_OPT_COORD_MODE:  // what the validate kernel of the current options uses
       *value = validate_coord_mode(t, t->opt_kernel == GBP_KERNEL_DIRECT);
+      return GBP_OK;
+    case GBP_OPT_REFILL_WINDOW:  // the persistent kernel's, at the current options
+      *value = refill_window(t, validate_coord_mode(t, false) == 1 ? stage_bytes(t->nx, t->ny) : 0,
+                             variant_lds(t));
       return GBP_OK;
     default: return GBP_E_INVALID_ARG;
   }

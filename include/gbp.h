@@ -155,10 +155,21 @@ int gbp_terrain_info(const gbp_terrain *t, int *nx, int *ny, int *storage,
 #define GBP_OPT_NN_STATS     18  /* 1: the matrix-core search counts its fp64 re-checks
                                     in gbp_plan_status.stat_nn_* (diagnostics: costs
                                     same-address atomics; default 0)                  */
+#define GBP_OPT_REFILL_WINDOW 19 /* read-only: rows per wave of the persistent validate
+                                    kernel's prefetch window at the current options
+                                    (0: every refill loads its rows itself)           */
 #define GBP_KERNEL_DIRECT     0  /* one lane per attempt                              */
 #define GBP_KERNEL_PERSISTENT 1  /* persistent waves, lanes re-packed per sample      */
 int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value);
 int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value);
+/* The LDS a persistent validate launch would request for an nx x ny terrain
+ * with straight-line brackets (no device needed): `block` threads per
+ * workgroup, `waves` per SIMD, `lds_max` bytes a workgroup may use.  Outputs
+ * (each may be NULL): coord_lds 1 when the coordinate vectors are staged in
+ * LDS, window the rows per wave of the refill's prefetch window (0: every
+ * refill loads its rows itself), bytes the dynamic LDS of the launch. */
+int gbp_validate_lds_plan(int nx, int ny, int64_t block, int64_t waves, size_t lds_max,
+                          int *coord_lds, int *window, size_t *bytes);
 
 /* ---- batched terrain queries ---------------------------------------------
  * FastTerrainMap::getGroundHeight + heightIsNan (fast_terrain_map.cpp:94-157)

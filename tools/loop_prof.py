@@ -8,7 +8,9 @@ The -DGBP_LOOP_PROF build of k_validate_persistent reads the shader clock
 refill, the helper plan, sample + isValidState, transition + the helpers'
 consumption, outputs + s_new ring; plus the whole loop, tail steps and steps.
 Config 3 (synth-rough-1024, 262,144 attempts) and config 2 (synth-rough-256,
-65,536), one launch each after a warm-up launch.
+65,536), one launch each after a warm-up launch; with --fresh-batches N the
+profiled launch is the last of 2 N that cycle N distinct resident batches
+(bench.py's inputs: no launch replays cache-warm rows).
 """
 import argparse
 import ctypes
@@ -28,7 +30,7 @@ from global_body_planner_amd import workload as W  # noqa: E402
 PHASES = ["refill", "helper_plan", "sample_isvalid", "transition_consume", "outputs_ring"]
 
 
-def run(lib, terrain, batch, seed, opts=(), waves=2048):
+def run(lib, terrain, batch, seed, opts=(), waves=2048, fresh=1):
     data = td.by_name(terrain)
     T = gbp.Terrain.from_data(data, device=0, lib=lib)
     for kv in opts:
@@ -36,7 +38,15 @@ def run(lib, terrain, batch, seed, opts=(), waves=2048):
         T.set_option(getattr(L, "OPT_" + k), int(v))
     s, act, d, _, _ = W.make_attempts(T, batch, seed)
     out = T.validate_pairs(s, act, d)
-    T.validate_pairs(s, act, d, out=out)
+    if fresh > 1:
+        # bench.py's fresh-batch protocol: distinct resident batches cycled, so the
+        # profiled launch (the last one) reads rows no earlier launch left in cache
+        ins = [(s, act, d)] + [W.make_attempts(T, batch, seed, index_base=k * batch)[:3]
+                               for k in range(1, fresh)]
+        for k in range(2 * fresh):
+            T.validate_pairs(*ins[k % fresh], out=out)
+    else:
+        T.validate_pairs(s, act, d, out=out)
     torch.cuda.synchronize()
     buf = (ctypes.c_ulonglong * (12 * waves))()
     rc = lib.gbp_loop_prof_read(buf, ctypes.c_int(waves))
@@ -57,6 +67,9 @@ def run(lib, terrain, batch, seed, opts=(), waves=2048):
     for k, nm in enumerate(PHASES):
         row[nm + "_frac"] = float(a[:, k].sum() / tot)
         row[nm + "_per_step"] = float(a[:, k].sum() / steps)
+    # a tail step refills nothing: the refill's cycles fall on the steps before the tail
+    row["refill_per_refilling_step"] = float(a[:, 0].sum() / max(1.0, (a[:, 7] - a[:, 6]).sum()))
+    row["inputs"] = f"fresh: {fresh} batches cycled" if fresh > 1 else "one batch replayed"
     # wall clock (s_memrealtime, 100 MHz): start skew, per-wave spans, the end
     t0, t1 = a[:, 8], a[:, 9]
     span = (t1 - t0) * 10.0  # ns
@@ -87,12 +100,14 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument("lib")
     p.add_argument("--set", action="append", default=[], help="OPT=value on the handle")
+    p.add_argument("--fresh-batches", type=int, default=1,
+                   help="cycle this many distinct resident batches (bench.py's protocol: 8)")
     a = p.parse_args()
     lib = L.load(a.lib)
     lib.gbp_loop_prof_read.argtypes = [ctypes.c_void_p, ctypes.c_int]
     for terrain, batch, seed in (("synth-rough-1024", 262144, W.CONFIG_SEEDS[3]),
                                  ("synth-rough-256", 65536, W.CONFIG_SEEDS[2])):
-        print(json.dumps(run(lib, terrain, batch, seed, a.set)), flush=True)
+        print(json.dumps(run(lib, terrain, batch, seed, a.set, fresh=a.fresh_batches)), flush=True)
 
 
 if __name__ == "__main__":
