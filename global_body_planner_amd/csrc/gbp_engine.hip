@@ -175,22 +175,6 @@ struct SnewRec {
 };
 constexpr int SN_RING = 2 * 64;  // entries per wave: < 64 left + up to 64 queued in a step
 
-// -DGBP_XWAVE (A/B variant): the workgroup-level helper
-// exchange.  Waves pair up (w, w ^ 1).  A wave whose own work is done does
-// not exit while its partner still runs: it becomes 64 more helpers of the
-// partner's owners.  Per step the partner (in its tail) publishes its owners'
-// (stage, t, ts, V) in its box and raises seq; the helper wave evaluates the
-// samples helpers n_idle .. n_idle + 63 would (same slot / owner rule, rows
-// read from the partner's LDS rows), writes the result words and raises ack;
-// the partner consumes them after its own helpers', in slot order.
-struct XBox {
-  int seq, ack, fin, n_idle;
-  unsigned long long act;
-  int st[64], row[64];
-  uint32_t vb[64], r0[64], r1[64];
-  double t[64], ts[64];
-};
-
 // (diagnostic build, -DGBP_LOOP_PROF: cycles per phase of the persistent loop,
 // per wave, read by gbp_loop_prof_read; tools/loop_prof.py)
 #ifdef GBP_LOOP_PROF
@@ -259,8 +243,6 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   double *const wave_rows = SA + (size_t)wv * (WAVE + pf) * SA_ROW;
   SnewRec *const ring = (SnewRec *)(SA + (size_t)nwv * (WAVE + pf) * SA_ROW) + wv * SN_RING;
   [[maybe_unused]] int *const Q = (int *)(ring + (nwv - wv) * SN_RING) + wv * pf;  // the window's slot queue
-  // behind the queues: the A/B variants' regions (GBP_XWAVE, GBP_LDS_TERRAIN)
-  [[maybe_unused]] void *const lds_extra = Q + (((nwv * pf + 1) & ~1) - wv * pf);
   // work source: a fixed contiguous slice [cur, end) per wave, handed out to
   // the wave's idle lanes in order (no atomics).  Dynamic dequeues (one or
   // eight device-scope heads, chunked, per-workgroup LDS queues; round 4: the
@@ -295,25 +277,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   int dir0 = dir_all;
   if ((unsigned int)lane < take0) load_row(cur + lane, row0, dir0);
 #endif
-#ifndef GBP_LDS_TERRAIN
   const TerrainView<ZT> T = CM == 1 ? stage_coords(T0, gbp_smem) : T0;
-#else
-  // A/B variant (upper bound of LDS terrain tiles): the
-  // whole x-pair height array staged in LDS behind the s_new rings (only
-  // terrains small enough: the host checks the fit), every gather from LDS
-  TerrainView<ZT> T = CM == 1 ? stage_coords(T0, gbp_smem) : T0;
-  {
-    ZT *zl = (ZT *)lds_extra;
-    const int nz = 2 * (T0.nx - 1) * T0.ny;  // ZT elements (even: 8-B aligned pairs)
-    typedef ZT zpair __attribute__((ext_vector_type(2)));
-    for (int i = threadIdx.x; i < nz / 2; i += blockDim.x)
-      ((zpair *)zl)[i] = ((const zpair *)T0.z)[i];
-    __syncthreads();
-#ifndef GBP_LDS_TERRAIN_STAGE_ONLY
-    T.z = zl;
-#endif
-  }
-#endif
   int ring_n = 0;  // wave-uniform
   // s_new of the ring's first cnt entries, one per lane (converged)
   auto flush = [&](int cnt) {
@@ -334,21 +298,6 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
       for (int k = 0; k < 8; k++) s_new[8 * (size_t)r.idx + k] = o[k];
     }
   };
-#ifdef GBP_XWAVE
-  XBox *const xbox = (XBox *)lds_extra;
-  XBox *const mybox = xbox + wv;
-  XBox *const pbox = xbox + (wv ^ 1);
-  const bool has_partner = (wv ^ 1) < (int)(blockDim.x / WAVE);
-  double *const partner_rows = SA + (size_t)(wv ^ 1) * (WAVE + pf) * SA_ROW;
-  if (lane == 0) {
-    mybox->seq = 0;
-    mybox->ack = 0;
-    mybox->fin = 0;
-  }
-  __syncthreads();
-  int myseq = 0, served = 0;
-  bool fin_sent = false;
-#endif
   Lane L;
   int row = lane;  // this lane's row slot among its wave's 64 + pf
   L.s = wave_rows + row * SA_ROW;
@@ -432,33 +381,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     }
 #endif
     const unsigned long long act = __ballot(L.stage != ST_IDLE);
-#ifdef GBP_XWAVE
-    // this wave's work is done: serve the partner's requests until it is done
-    bool serve = false;
-    if (!act) {
-      if (!has_partner) break;
-      if (!fin_sent) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if (lane == 0) __hip_atomic_store(&mybox->fin, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        fin_sent = true;
-      }
-      int pseq, pfin;
-      for (;;) {
-        pseq = __builtin_amdgcn_readfirstlane(
-            __hip_atomic_load(&pbox->seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-        pfin = __builtin_amdgcn_readfirstlane(
-            __hip_atomic_load(&pbox->fin, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-        if (pseq != served || pfin) break;
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (pseq == served) break;  // the partner finished with no request pending
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-      served = pseq;
-      serve = true;
-    }
-#else
     if (!act) break;
-#endif
     LP_T(t1);
     LP_ADD(0, t0, t1);
     const bool owner = L.stage != ST_IDLE;
@@ -478,43 +401,6 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     double t_eval = owner ? stage_time(L) : 0.0;
     uint32_t vbase = L.acc.V;
     bool has = owner;
-#ifdef GBP_XWAVE
-    // a tail step with the partner free: publish the owners' loop state
-    bool xhelp = false;
-    if (tail && !serve && has_partner) {
-      xhelp = __builtin_amdgcn_readfirstlane(
-                  __hip_atomic_load(&pbox->fin, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != 0;
-      if (xhelp) {
-        mybox->st[lane] = L.stage;
-        mybox->row[lane] = row;
-        mybox->t[lane] = L.t;
-        mybox->ts[lane] = L.ts;
-        mybox->vb[lane] = L.acc.V;
-        if (lane == 0) {
-          mybox->act = act;
-          mybox->n_idle = WAVE - n_act;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        myseq++;
-        if (lane == 0) __hip_atomic_store(&mybox->seq, myseq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-    }
-    if (serve) {
-      // helper n_idle + lane of the partner's owners (the rule of the tail below)
-      const unsigned long long pact = pbox->act;
-      const int pn = __popcll(pact);
-      const int j = pbox->n_idle + lane;
-      const int src = nth_set_bit(pact, j % pn);
-      slot = 1 + j / pn;
-      ps = partner_rows + pbox->row[src] * SA_ROW;
-      st = pbox->st[src];
-      double t = pbox->t[src], ts = pbox->ts[src];
-      vbase = pbox->vb[src];
-      has = true;
-      for (int k = 0; k < slot && has; k++) has = advance_on_success<ADAPTIVE>(st, ps + 8, t, ts);
-      t_eval = sample_time(st, ps + 8, t);
-    } else
-#endif
     if (tail) {
       const unsigned long long idle = ~act;
       const int j = __popcll(idle & lt_mask);
@@ -543,16 +429,6 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     }
     LP_T(t3);
     LP_ADD(2, t2, t3);
-#ifdef GBP_XWAVE
-    if (serve) {  // the results, then the acknowledgement
-      pbox->r0[lane] = (acc_s.flags & 0xFFFFu) | (ok ? 1u << 16 : 0u) | (has ? 1u << 17 : 0u) |
-                       ((acc_s.V - (vbase + (uint32_t)slot)) << 18);
-      pbox->r1[lane] = acc_s.G;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      if (lane == 0) __hip_atomic_store(&pbox->ack, served, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      continue;
-    }
-#endif
     bool decided = false;
     if (owner) {  // the lane's own sample
       L.acc.G += acc_s.G;
@@ -563,19 +439,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     if (tail) {  // consume helper results in slot order
       const unsigned long long idle = ~act;
       const int n_idle = WAVE - n_act;
-#ifdef GBP_XWAVE
-      // the partner's 64 helpers come after this wave's own (helpers n_idle ..)
-      int n_help = n_idle;
-      if (xhelp) {
-        while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(
-                   &mybox->ack, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) != myseq)
-          __builtin_amdgcn_s_sleep(1);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        n_help += WAVE;
-      }
-#else
       const int n_help = n_idle;
-#endif
       const uint32_t w0 = (acc_s.flags & 0xFFFFu) | (ok ? 1u << 16 : 0u) | (has ? 1u << 17 : 0u) |
                           ((acc_s.V - (vbase + (uint32_t)slot)) << 18);
       const uint32_t w1 = acc_s.G;
@@ -591,13 +455,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
         const int j = (k - 1) * n_act + my_rank;
         const bool exists = owner && j < n_help;
         const int src = (exists && j < n_idle) ? nth_set_bit(idle, j) : lane;
-        uint32_t r0 = __shfl(w0, src), r1 = __shfl(w1, src);
-#ifdef GBP_XWAVE
-        if (exists && j >= n_idle) {
-          r0 = mybox->r0[j - n_idle];
-          r1 = mybox->r1[j - n_idle];
-        }
-#endif
+        const uint32_t r0 = __shfl(w0, src), r1 = __shfl(w1, src);
         if (chain && exists && ((r0 >> 17) & 1u)) {
           L.acc.G += r1;
           L.acc.V += (r0 >> 18) & 1u;
@@ -618,22 +476,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     lp[7] += 1;
 #endif
     const bool fin = owner && decided;
-#ifdef GBP_SNEW_IMMEDIATE
-    // A/B variant: the deciding lane forms s_new from its LDS row at once
-    // (round 3's form; no ring, no re-read of the rows)
-    if (fin && s_new && L.snew_kind != SN_NONE) {
-      double o[8];
-      sample_state(L.s, L.a,
-                   L.snew_kind == SN_STANCE_S ? ST_FWD_STANCE
-                                              : (L.snew_kind == SN_FLIGHT_B ? ST_FWD_LAND : ST_REV_STANCE),
-                   L.snew_p, o);
-#pragma unroll
-      for (int k = 0; k < 8; k++) s_new[8 * (size_t)L.idx + k] = o[k];
-    }
-    const bool queue = false;
-#else
     const bool queue = fin && s_new && L.snew_kind != SN_NONE;
-#endif
     if (fin) {
       const size_t i = (size_t)L.idx;
       uint32_t f = L.f | L.acc.flags;
@@ -1077,8 +920,7 @@ int coord_mode(const gbp_terrain *t, bool lds_ok) {
 int validate_coord_mode(const gbp_terrain *t, bool direct) {
   // the attempt rows and s_new rings are the persistent kernel's alone
   // (launch_validate_w allocates neither for the direct kernel)
-  const size_t rows =
-      direct ? 0 : (sizeof(double) * SA_ROW + sizeof(SnewRec) * SN_RING / WAVE) * (size_t)t->opt_block;
+  const size_t rows = direct ? 0 : rows_bytes((int)t->opt_block, 0);
   const size_t per_cu = std::max<int64_t>(1, t->opt_waves * 256 / t->opt_block) *
                         (stage_bytes(t->nx, t->ny) + rows);
   const bool lds_ok = t->opt_lds_coords && stage_bytes(t->nx, t->ny) + rows <= t->lds_max &&
@@ -1095,24 +937,15 @@ int validate_coord_mode(const gbp_terrain *t, bool direct) {
 // a workgroup's limit and among the workgroups that share a CU's 160 KB; 0
 // (every refill loads its rows itself) when nothing fits.  The coordinate mode
 // is chosen first (validate_coord_mode) and never gives way to the window.
-// LDS of the A/B variants' own regions behind the rows (GBP_LDS_TERRAIN sizes its own)
-inline size_t variant_lds(const gbp_terrain *t) {
-#ifdef GBP_XWAVE
-  return sizeof(XBox) * (size_t)(t->opt_block / WAVE);  // the helper exchange's boxes
-#else
-  return 0;
-#endif
-}
-
-int refill_window(const gbp_terrain *t, size_t coords, size_t extra) {
-#if !defined(GBP_REFILL_WINDOW) || defined(GBP_LDS_TERRAIN)
+int refill_window(const gbp_terrain *t, size_t coords) {
+#ifndef GBP_REFILL_WINDOW
   return 0;  // the default build has no window
 #else
   const int block = (int)t->opt_block;
   const size_t wgs = (size_t)std::max<int64_t>(1, t->opt_waves * 256 / block);
   const size_t cap = std::min<size_t>(t->lds_max, 160 * 1024 / wgs);
   for (int pf = PF_MAX; pf > 0; pf--)
-    if (coords + rows_bytes(block, pf) + extra <= cap) return pf;
+    if (coords + rows_bytes(block, pf) <= cap) return pf;
   return 0;
 #endif
 }
@@ -1150,15 +983,9 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
       // waves starting with idle lanes that help from the first step
       // (65,536 attempts: 0.084 -> 0.072 ms; 262,144: unchanged)
       const int64_t g = std::max<int64_t>(1, std::min<int64_t>(resident, (m + WAVE - 1) / WAVE));
-#ifdef GBP_LDS_TERRAIN
-      const size_t zb = sizeof(ZT) * 2 * (size_t)(t->nx - 1) * t->ny;
-      if (coords + rows_bytes(block, 0) + zb > t->lds_max) return GBP_E_SHAPE;  // the A/B variant only
-#else
-      const size_t zb = variant_lds(t);
-#endif
-      const int pf = refill_window(t, coords, zb);
+      const int pf = refill_window(t, coords);
       hipLaunchKernelGGL((k_validate_persistent<ZT, AD, W, CM, ONE>), dim3((unsigned)g), dim3(block),
-                         coords + rows_bytes(block, pf) + zb, st, T, (int)m, s + 8 * off, a + 10 * off, d, dir_all,
+                         coords + rows_bytes(block, pf), st, T, (int)m, s + 8 * off, a + 10 * off, d, dir_all,
                          v, sn, tn, flags + off, c, n_dev, (int)t->opt_helpers, (int)t->opt_xcd_map, pf);
     }
     HIPCHK(hipGetLastError());
@@ -1279,20 +1106,52 @@ bool affine_fit(const double *d, int n, double *a, double *h, int *base) {
 
 // host-pointer entry points: one synchronous staging round trip through the
 // handle's workspace on its private stream (used by the C++ adapters that
-// re-export the reference API).
+// re-export the reference API).  An entry point states its device arrays once,
+// as a list of take calls; the list runs twice: against a null base (sizing
+// mode: only `off` advances) for the byte count the buffer is allocated with,
+// then against that buffer, which it may not outgrow.
 struct Stage {
-  gbp_terrain *t;
-  char *base;
-  size_t off = 0;
+  char *base = nullptr;  // null: the sizing pass
+  size_t cap = 0, off = 0;
   template <class T>
-  T *take(size_t count) {
+  void take(T *&p, size_t count) {
     off = (off + 255) & ~(size_t)255;
-    T *p = (T *)(base + off);
+    p = base && off + count * sizeof(T) <= cap ? (T *)(base + off) : nullptr;
     off += count * sizeof(T);
-    return p;
   }
 };
-size_t rnd(size_t b) { return (b + 255) & ~(size_t)255; }
+template <class F>
+size_t stage_bytes_of(F &carve) {
+  Stage S;
+  carve(S);
+  return S.off;
+}
+template <class F>
+int stage_carve(void *buf, size_t cap, F &carve) {
+  Stage S{(char *)buf, cap};
+  carve(S);
+  return S.off <= cap ? GBP_OK : GBP_E_ALLOC;
+}
+// the list carved from the handle's workspace, grown first if it is smaller
+template <class F>
+int stage_ws(gbp_terrain *t, F carve) {
+  const int rc = ensure_ws(&t->ws, &t->ws_bytes, stage_bytes_of(carve));
+  return rc ? rc : stage_carve(t->ws, t->ws_bytes, carve);
+}
+// the list carved from a device buffer of its own, freed at scope exit (the
+// entry points without a terrain handle)
+struct DevBuf {
+  void *p = nullptr;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+template <class F>
+int stage_buf(DevBuf &b, F carve) {
+  const size_t need = stage_bytes_of(carve);
+  if (hipMalloc(&b.p, need) != hipSuccess) return GBP_E_ALLOC;
+  return stage_carve(b.p, need, carve);
+}
 
 }  // namespace
 
@@ -1338,10 +1197,10 @@ int gbp_validate_lds_plan(int nx, int ny, int64_t block, int64_t waves, size_t l
   t.lds_max = lds_max;
   const int cm = validate_coord_mode(&t, false);
   const size_t coords = cm == 1 ? stage_bytes(nx, ny) : 0;
-  const int pf = refill_window(&t, coords, variant_lds(&t));
+  const int pf = refill_window(&t, coords);
   if (coord_lds) *coord_lds = cm == 1;
   if (window) *window = pf;
-  if (bytes) *bytes = coords + rows_bytes((int)block, pf) + variant_lds(&t);
+  if (bytes) *bytes = coords + rows_bytes((int)block, pf);
   return GBP_OK;
 }
 
@@ -1592,8 +1451,7 @@ int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value) {
       *value = validate_coord_mode(t, t->opt_kernel == GBP_KERNEL_DIRECT);
       return GBP_OK;
     case GBP_OPT_REFILL_WINDOW:  // the persistent kernel's, at the current options
-      *value = refill_window(t, validate_coord_mode(t, false) == 1 ? stage_bytes(t->nx, t->ny) : 0,
-                             variant_lds(t));
+      *value = refill_window(t, validate_coord_mode(t, false) == 1 ? stage_bytes(t->nx, t->ny) : 0);
       return GBP_OK;
     default: return GBP_E_INVALID_ARG;
   }
@@ -1922,11 +1780,10 @@ int gbp_height_batch_host(gbp_terrain *t, int64_t n, const double *xy, double *h
   if (n <= 0) return n == 0 ? GBP_OK : GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes, rnd(16 * n) + rnd(8 * n) + 2 * rnd(n) + 1024);
+  double *dxy, *dh;
+  uint8_t *dn, *dood;
+  int rc = stage_ws(t, [&](Stage &S) { S.take(dxy, 2 * n); S.take(dh, n); S.take(dn, n); S.take(dood, n); });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *dxy = S.take<double>(2 * n), *dh = S.take<double>(n);
-  uint8_t *dn = S.take<uint8_t>(n), *dood = S.take<uint8_t>(n);
   H2D(dxy, xy, 16 * n);
   rc = gbp_height_batch_dev(t, n, dxy, dh, dn, dood, st);
   if (rc) return rc;
@@ -1944,11 +1801,10 @@ int gbp_normal_batch_host(gbp_terrain *t, int64_t n, const double *xy, double *n
   if (!normal) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes, rnd(16 * n) + rnd(24 * n) + rnd(n) + 1024);
+  double *dxy, *dn;
+  uint8_t *dood;
+  int rc = stage_ws(t, [&](Stage &S) { S.take(dxy, 2 * n); S.take(dn, 3 * n); S.take(dood, n); });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *dxy = S.take<double>(2 * n), *dn = S.take<double>(3 * n);
-  uint8_t *dood = S.take<uint8_t>(n);
   H2D(dxy, xy, 16 * n);
   rc = gbp_normal_batch_dev(t, n, dxy, dn, dood, st);
   if (rc) return rc;
@@ -1964,13 +1820,13 @@ int gbp_valid_states_host(gbp_terrain *t, int64_t n, const double *states, const
   if (n <= 0) return n == 0 ? GBP_OK : GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes,
-                     rnd(64 * n) + 2 * rnd(n) + 2 * rnd(4 * n) + 2048);
+  double *ds;
+  uint8_t *dp, *dv;
+  uint32_t *df, *dc;
+  int rc = stage_ws(t, [&](Stage &S) {
+    S.take(ds, 8 * n); S.take(dp, n); S.take(dv, n); S.take(df, n); S.take(dc, n);
+  });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *ds = S.take<double>(8 * n);
-  uint8_t *dp = S.take<uint8_t>(n), *dv = S.take<uint8_t>(n);
-  uint32_t *df = S.take<uint32_t>(n), *dc = S.take<uint32_t>(n);
   H2D(ds, states, 64 * n);
   if (phase) H2D(dp, phase, n);
   rc = gbp_valid_states_dev(t, n, ds, phase ? dp : nullptr, phase_all, dv, df, dc, st);
@@ -1994,15 +1850,14 @@ int gbp_validate_pairs_host(gbp_terrain *t, int64_t n, const double *s, const do
   if (!s || !a) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes,
-                     rnd(64 * n) + rnd(80 * n) + rnd(64 * n) + rnd(8 * n) + 2 * rnd(n) +
-                         2 * rnd(4 * n) + 4096);
+  double *ds, *da, *dsn, *dtn;
+  uint8_t *dd, *dv;
+  uint32_t *df, *dc;
+  int rc = stage_ws(t, [&](Stage &S) {
+    S.take(ds, 8 * n); S.take(da, 10 * n); S.take(dsn, 8 * n); S.take(dtn, n);
+    S.take(dd, n); S.take(dv, n); S.take(df, n); S.take(dc, n);
+  });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *ds = S.take<double>(8 * n), *da = S.take<double>(10 * n);
-  double *dsn = S.take<double>(8 * n), *dtn = S.take<double>(n);
-  uint8_t *dd = S.take<uint8_t>(n), *dv = S.take<uint8_t>(n);
-  uint32_t *df = S.take<uint32_t>(n), *dc = S.take<uint32_t>(n);
   H2D(ds, s, 64 * n);
   H2D(da, a, 80 * n);
   if (direction) H2D(dd, direction, n);
@@ -2043,15 +1898,15 @@ int gbp_extend_batch_host(gbp_terrain *t, int64_t n, const double *s_near, const
   if (!s_near || !target || !result || !s_new || !a_new) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes,
-                     3 * rnd(64 * n) + rnd(80 * n) + rnd(n) + 4 * rnd(4 * n) + 4096);
+  double *dsn, *dtg, *dnew, *danew;
+  uint8_t *dd;
+  int32_t *dr, *dch;
+  uint32_t *dc, *df;
+  int rc = stage_ws(t, [&](Stage &S) {
+    S.take(dsn, 8 * n); S.take(dtg, 8 * n); S.take(dnew, 8 * n); S.take(danew, 10 * n);
+    S.take(dd, n); S.take(dr, n); S.take(dch, n); S.take(dc, n); S.take(df, n);
+  });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *dsn = S.take<double>(8 * n), *dtg = S.take<double>(8 * n);
-  double *dnew = S.take<double>(8 * n), *danew = S.take<double>(10 * n);
-  uint8_t *dd = S.take<uint8_t>(n);
-  int32_t *dr = S.take<int32_t>(n), *dch = S.take<int32_t>(n);
-  uint32_t *dc = S.take<uint32_t>(n), *df = S.take<uint32_t>(n);
   H2D(dsn, s_near, 64 * n);
   H2D(dtg, target, 64 * n);
   H2D(dnew, s_new, 64 * n);
@@ -2086,11 +1941,10 @@ int gbp_sample_states_host(gbp_terrain *t, int64_t n, uint64_t seed, uint64_t st
   if (!states) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes, rnd(64 * n) + rnd(4 * n) + 1024);
+  double *ds;
+  int32_t *dt;
+  int rc = stage_ws(t, [&](Stage &S) { S.take(ds, 8 * n); S.take(dt, n); });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *ds = S.take<double>(8 * n);
-  int32_t *dt = S.take<int32_t>(n);
   rc = gbp_sample_states_dev(t, n, seed, stream_id, index_base, require_phase, max_tries, ds, dt,
                              st);
   if (rc) return rc;
@@ -2108,10 +1962,9 @@ int gbp_sample_states_dir_host(gbp_terrain *t, int64_t n, uint64_t seed, uint64_
   if (!states || !s_from || !s_to) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes, rnd(64 * n) + 1024);
+  double *ds;
+  int rc = stage_ws(t, [&](Stage &S) { S.take(ds, 8 * n); });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *ds = S.take<double>(8 * n);
   rc = gbp_sample_states_dir_dev(t, n, seed, stream_id, index_base, cfg, s_from, s_to, ds, st);
   if (rc) return rc;
   D2H(states, ds, 64 * n);
@@ -2128,12 +1981,12 @@ int gbp_sample_actions_dir_host(gbp_terrain *t, int64_t n, const double *normals
   if (!normals || !s || !s_near || !actions) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes, rnd(24 * n) + 2 * rnd(64 * n) + rnd(n) + rnd(80 * n) + 2048);
+  double *dn, *ds, *dsn, *da;
+  uint8_t *dd;
+  int rc = stage_ws(t, [&](Stage &S) {
+    S.take(dn, 3 * n); S.take(ds, 8 * n); S.take(dsn, 8 * n); S.take(dd, n); S.take(da, 10 * n);
+  });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *dn = S.take<double>(3 * n), *ds = S.take<double>(8 * n), *dsn = S.take<double>(8 * n);
-  uint8_t *dd = S.take<uint8_t>(n);
-  double *da = S.take<double>(10 * n);
   H2D(dn, normals, 24 * n);
   H2D(ds, s, 64 * n);
   H2D(dsn, s_near, 64 * n);
@@ -2153,10 +2006,9 @@ int gbp_sample_actions_host(gbp_terrain *t, int64_t n, const double *normals, ui
   if (!normals || !actions) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
-  int rc = ensure_ws(&t->ws, &t->ws_bytes, rnd(24 * n) + rnd(80 * n) + 1024);
+  double *dn, *da;
+  int rc = stage_ws(t, [&](Stage &S) { S.take(dn, 3 * n); S.take(da, 10 * n); });
   if (rc) return rc;
-  Stage S{t, (char *)t->ws};
-  double *dn = S.take<double>(3 * n), *da = S.take<double>(10 * n);
   H2D(dn, normals, 24 * n);
   rc = gbp_sample_actions_dev(n, dn, seed, stream_id, index_base, da, st);
   if (rc) return rc;
@@ -2165,32 +2017,31 @@ int gbp_sample_actions_host(gbp_terrain *t, int64_t n, const double *normals, ui
   return GBP_OK;
 }
 
+// the terrain-less entries: a buffer of their own, synchronous copies on the
+// null stream; an empty tree or output still stages one element, so the
+// pointer passed down is valid
+#define H2D0(dst, src, bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice))
+#define D2H0(dst, src, bytes) HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost))
+#define NV1(n) ((size_t)((n) > 0 ? (n) : 1))
+
 int gbp_nearest_batch_host(int64_t n_query, const double *queries, int64_t n_vert,
                            const double *vertices, int32_t *index, double *dist) {
   if (n_query <= 0) return n_query == 0 ? GBP_OK : GBP_E_INVALID_ARG;
   if (!queries || !index || (n_vert > 0 && !vertices)) return GBP_E_INVALID_ARG;
-  void *buf = nullptr;
-  const size_t need = rnd(64 * n_query) + rnd(64 * (n_vert > 0 ? n_vert : 1)) +
-                      rnd(4 * n_query) + rnd(8 * n_query) + 1024;
-  if (hipMalloc(&buf, need) != hipSuccess) return GBP_E_ALLOC;
-  char *p = (char *)buf;
-  double *dq = (double *)p; p += rnd(64 * n_query);
-  double *dv = (double *)p; p += rnd(64 * (n_vert > 0 ? n_vert : 1));
-  int32_t *di = (int32_t *)p; p += rnd(4 * n_query);
-  double *dd = (double *)p;
-  hipStream_t st = nullptr;
-  int rc = GBP_OK;
-  if (hipMemcpy(dq, queries, 64 * n_query, hipMemcpyHostToDevice) != hipSuccess) rc = GBP_E_HIP;
-  if (!rc && n_vert > 0 &&
-      hipMemcpy(dv, vertices, 64 * n_vert, hipMemcpyHostToDevice) != hipSuccess)
-    rc = GBP_E_HIP;
-  if (!rc) rc = gbp_nearest_batch_dev(n_query, dq, n_vert, dv, di, dd, st);
-  if (!rc && hipMemcpy(index, di, 4 * n_query, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = GBP_E_HIP;
-  if (!rc && dist && hipMemcpy(dist, dd, 8 * n_query, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = GBP_E_HIP;
-  (void)hipFree(buf);
-  return rc;
+  double *dq, *dv, *dd;
+  int32_t *di;
+  DevBuf buf;
+  int rc = stage_buf(buf, [&](Stage &S) {
+    S.take(dq, 8 * n_query); S.take(dv, 8 * NV1(n_vert)); S.take(di, n_query); S.take(dd, n_query);
+  });
+  if (rc) return rc;
+  H2D0(dq, queries, 64 * n_query);
+  if (n_vert > 0) H2D0(dv, vertices, 64 * n_vert);
+  rc = gbp_nearest_batch_dev(n_query, dq, n_vert, dv, di, dd, nullptr);
+  if (rc) return rc;
+  D2H0(index, di, 4 * n_query);
+  if (dist) D2H0(dist, dd, 8 * n_query);
+  return GBP_OK;
 }
 
 int gbp_neighbors_batch_host(int64_t n_query, const double *queries, int64_t n_vert,
@@ -2199,28 +2050,21 @@ int gbp_neighbors_batch_host(int64_t n_query, const double *queries, int64_t n_v
   if (n_query <= 0) return n_query == 0 ? GBP_OK : GBP_E_INVALID_ARG;
   if (!queries || !count || max_out < 0 || (max_out > 0 && !out) || (n_vert > 0 && !vertices))
     return GBP_E_INVALID_ARG;
-  void *buf = nullptr;
   const size_t nout = (size_t)n_query * (size_t)max_out;
-  const size_t need = rnd(64 * n_query) + rnd(64 * (n_vert > 0 ? n_vert : 1)) +
-                      rnd(4 * (nout > 0 ? nout : 1)) + rnd(4 * n_query) + 1024;
-  if (hipMalloc(&buf, need) != hipSuccess) return GBP_E_ALLOC;
-  char *p = (char *)buf;
-  double *dq = (double *)p; p += rnd(64 * n_query);
-  double *dv = (double *)p; p += rnd(64 * (n_vert > 0 ? n_vert : 1));
-  int32_t *dout = (int32_t *)p; p += rnd(4 * (nout > 0 ? nout : 1));
-  int32_t *dc = (int32_t *)p;
-  int rc = GBP_OK;
-  if (hipMemcpy(dq, queries, 64 * n_query, hipMemcpyHostToDevice) != hipSuccess) rc = GBP_E_HIP;
-  if (!rc && n_vert > 0 &&
-      hipMemcpy(dv, vertices, 64 * n_vert, hipMemcpyHostToDevice) != hipSuccess)
-    rc = GBP_E_HIP;
-  if (!rc) rc = gbp_neighbors_batch_dev(n_query, dq, n_vert, dv, radius, max_out, dout, dc, nullptr);
-  if (!rc && nout > 0 && hipMemcpy(out, dout, 4 * nout, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = GBP_E_HIP;
-  if (!rc && hipMemcpy(count, dc, 4 * n_query, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = GBP_E_HIP;
-  (void)hipFree(buf);
-  return rc;
+  double *dq, *dv;
+  int32_t *dout, *dc;
+  DevBuf buf;
+  int rc = stage_buf(buf, [&](Stage &S) {
+    S.take(dq, 8 * n_query); S.take(dv, 8 * NV1(n_vert)); S.take(dout, NV1(nout)); S.take(dc, n_query);
+  });
+  if (rc) return rc;
+  H2D0(dq, queries, 64 * n_query);
+  if (n_vert > 0) H2D0(dv, vertices, 64 * n_vert);
+  rc = gbp_neighbors_batch_dev(n_query, dq, n_vert, dv, radius, max_out, dout, dc, nullptr);
+  if (rc) return rc;
+  if (nout > 0) D2H0(out, dout, 4 * nout);
+  D2H0(count, dc, 4 * n_query);
+  return GBP_OK;
 }
 
 int gbp_knn_batch_host(int64_t n_query, const double *queries, int64_t n_vert,
@@ -2228,27 +2072,21 @@ int gbp_knn_batch_host(int64_t n_query, const double *queries, int64_t n_vert,
   if (n_query <= 0) return n_query == 0 ? GBP_OK : GBP_E_INVALID_ARG;
   if (!queries || !out || n_nearest < 1 || n_nearest > GBP_KNN_MAX || (n_vert > 0 && !vertices))
     return GBP_E_INVALID_ARG;
-  void *buf = nullptr;
   const size_t nout = (size_t)n_query * (size_t)n_nearest;
-  const size_t need = rnd(64 * n_query) + rnd(64 * (n_vert > 0 ? n_vert : 1)) + rnd(4 * nout) +
-                      rnd(8 * nout) + 1024;
-  if (hipMalloc(&buf, need) != hipSuccess) return GBP_E_ALLOC;
-  char *p = (char *)buf;
-  double *dq = (double *)p; p += rnd(64 * n_query);
-  double *dv = (double *)p; p += rnd(64 * (n_vert > 0 ? n_vert : 1));
-  int32_t *dout = (int32_t *)p; p += rnd(4 * nout);
-  double *dd = (double *)p;
-  int rc = GBP_OK;
-  if (hipMemcpy(dq, queries, 64 * n_query, hipMemcpyHostToDevice) != hipSuccess) rc = GBP_E_HIP;
-  if (!rc && n_vert > 0 &&
-      hipMemcpy(dv, vertices, 64 * n_vert, hipMemcpyHostToDevice) != hipSuccess)
-    rc = GBP_E_HIP;
-  if (!rc) rc = gbp_knn_batch_dev(n_query, dq, n_vert, dv, n_nearest, dout, dd, nullptr);
-  if (!rc && hipMemcpy(out, dout, 4 * nout, hipMemcpyDeviceToHost) != hipSuccess) rc = GBP_E_HIP;
-  if (!rc && dist && hipMemcpy(dist, dd, 8 * nout, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = GBP_E_HIP;
-  (void)hipFree(buf);
-  return rc;
+  double *dq, *dv, *dd;
+  int32_t *dout;
+  DevBuf buf;
+  int rc = stage_buf(buf, [&](Stage &S) {
+    S.take(dq, 8 * n_query); S.take(dv, 8 * NV1(n_vert)); S.take(dout, nout); S.take(dd, nout);
+  });
+  if (rc) return rc;
+  H2D0(dq, queries, 64 * n_query);
+  if (n_vert > 0) H2D0(dv, vertices, 64 * n_vert);
+  rc = gbp_knn_batch_dev(n_query, dq, n_vert, dv, n_nearest, dout, dd, nullptr);
+  if (rc) return rc;
+  D2H0(out, dout, 4 * nout);
+  if (dist) D2H0(dist, dd, 8 * nout);
+  return GBP_OK;
 }
 
 int gbp_knn_yaw_batch_host(int64_t n_query, const double *queries, int64_t n_vert,
@@ -2258,40 +2096,30 @@ int gbp_knn_yaw_batch_host(int64_t n_query, const double *queries, int64_t n_ver
   if (!queries || !out || n_nearest < 1 || n_nearest > GBP_KNN_MAX || (n_vert > 0 && !vertices))
     return GBP_E_INVALID_ARG;
   // the yaws with glibc (planning_utils.h:135-136), as the reference forms them
-  const int64_t nv = n_vert > 0 ? n_vert : 1;
-  std::vector<double> qy((size_t)n_query), vy((size_t)nv, 0.0);
+  const size_t nv = NV1(n_vert);
+  std::vector<double> qy((size_t)n_query), vy(nv, 0.0);
   for (int64_t i = 0; i < n_query; i++) qy[i] = gbp_host_yaw(queries + 8 * i);
   for (int64_t j = 0; j < n_vert; j++) vy[j] = gbp_host_yaw(vertices + 8 * j);
-  void *buf = nullptr;
   const size_t nout = (size_t)n_query * (size_t)n_nearest;
-  const size_t need = rnd(64 * n_query) + rnd(64 * nv) + rnd(8 * n_query) + rnd(8 * nv) +
-                      rnd(4 * nout) + rnd(8 * nout) + 1024;
-  if (hipMalloc(&buf, need) != hipSuccess) return GBP_E_ALLOC;
-  char *p = (char *)buf;
-  double *dq = (double *)p; p += rnd(64 * n_query);
-  double *dv = (double *)p; p += rnd(64 * nv);
-  double *dqy = (double *)p; p += rnd(8 * n_query);
-  double *dvy = (double *)p; p += rnd(8 * nv);
-  int32_t *dout = (int32_t *)p; p += rnd(4 * nout);
-  double *dd = (double *)p;
-  int rc = GBP_OK;
-  if (hipMemcpy(dq, queries, 64 * n_query, hipMemcpyHostToDevice) != hipSuccess) rc = GBP_E_HIP;
-  if (!rc && hipMemcpy(dqy, qy.data(), 8 * n_query, hipMemcpyHostToDevice) != hipSuccess)
-    rc = GBP_E_HIP;
-  if (!rc && n_vert > 0 &&
-      (hipMemcpy(dv, vertices, 64 * n_vert, hipMemcpyHostToDevice) != hipSuccess ||
-       hipMemcpy(dvy, vy.data(), 8 * n_vert, hipMemcpyHostToDevice) != hipSuccess))
-    rc = GBP_E_HIP;
-  if (!rc)
-    rc = gbp_knn_yaw_batch_dev(n_query, dq, dqy, n_vert, dv, dvy, length_weight, yaw_weight,
-                               n_nearest, dout, dd, nullptr);
-  if (!rc && hipMemcpy(out, dout, 4 * nout, hipMemcpyDeviceToHost) != hipSuccess) rc = GBP_E_HIP;
-  if (!rc && dist && hipMemcpy(dist, dd, 8 * nout, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = GBP_E_HIP;
-  (void)hipFree(buf);
-  return rc;
+  double *dq, *dv, *dqy, *dvy, *dd;
+  int32_t *dout;
+  DevBuf buf;
+  int rc = stage_buf(buf, [&](Stage &S) {
+    S.take(dq, 8 * n_query); S.take(dv, 8 * nv); S.take(dqy, n_query); S.take(dvy, nv);
+    S.take(dout, nout); S.take(dd, nout);
+  });
+  if (rc) return rc;
+  H2D0(dq, queries, 64 * n_query);
+  H2D0(dqy, qy.data(), 8 * n_query);
+  if (n_vert > 0) H2D0(dv, vertices, 64 * n_vert);
+  if (n_vert > 0) H2D0(dvy, vy.data(), 8 * n_vert);
+  rc = gbp_knn_yaw_batch_dev(n_query, dq, dqy, n_vert, dv, dvy, length_weight, yaw_weight,
+                             n_nearest, dout, dd, nullptr);
+  if (rc) return rc;
+  D2H0(out, dout, 4 * nout);
+  if (dist) D2H0(dist, dd, 8 * nout);
+  return GBP_OK;
 }
-
 // ---- FRAGILE attempts: the glibc re-decision (host/gbp_host_check.cpp) ------------
 int gbp_resolve_fragile_host(gbp_terrain *t, int64_t n, const double *s, const double *a,
                              const uint8_t *direction, int direction_all, int adaptive,

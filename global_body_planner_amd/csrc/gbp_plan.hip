@@ -545,22 +545,19 @@ __device__ __forceinline__ void nh_sweep(const _Float16 *__restrict__ vh, int c0
   const int lane = threadIdx.x & (WAVE - 1), r = lane & 31, h = lane >> 5;
   const nh8 *base = (const nh8 *)vh + (NH_ROW / 8) * r + h;
   constexpr int64_t CS = NH_ROW * 4;  // nh8 per chunk
-  // tile u's minimum over its lane-unit: the scores of chunks c and c + 1
-  // (TAIL: rows past nv masked, chunk c + 1 absent when c + 1 >= c1)
-  auto unit_min = [&](int u, int c, const nh8 (&a)[4], auto tail_tag) {
-    constexpr bool TAIL = decltype(tail_tag)::value;
+  // tile u's minimum over the last lane-unit: the scores of chunks c and c + 1
+  // (rows past nv masked, chunk c + 1 absent when c + 1 >= c1)
+  auto unit_min = [&](int u, int c, const nh8 (&a)[4]) {
     float m = INFINITY;
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-      if (TAIL && c + k >= c1) break;
+      if (c + k >= c1) break;
       nhacc acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * k], b1[u], nhacc{}, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2 * k + 1], b2[u], acc, 0, 0, 0);
-      if (TAIL) {
-        const int rem = nv - 32 * (c + k);
+      const int rem = nv - 32 * (c + k);
 #pragma unroll
-        for (int i = 0; i < 16; i++)
-          if ((i & 3) + 8 * (i >> 2) + 4 * h >= rem) acc[i] = INFINITY;
-      }
+      for (int i = 0; i < 16; i++)
+        if ((i & 3) + 8 * (i >> 2) + 4 * h >= rem) acc[i] = INFINITY;
       m = k ? nh_min2(m, nh_min16(acc)) : nh_min16(acc);
     }
     return m;
@@ -574,12 +571,11 @@ __device__ __forceinline__ void nh_sweep(const _Float16 *__restrict__ vh, int c0
   // full units, the next unit's rows in flight while one is scored; a
   // scheduling barrier per tile keeps one tile's accumulators live at a time
   const int uf = min(c1, nv >> 5) & ~1;  // chunks [c0, uf) form full units
-#ifndef GBP_NN_SERIAL
   // Full units, software-pipelined over two accumulators: a chunk's scores
   // (two MFMAs) are reduced while the next chunk's MFMAs run, so the wave's
   // VALU minimum and top-3 insert overlap its own matrix work instead of
-  // waiting for it (the serial form, -DGBP_NN_SERIAL, scores a tile's two
-  // chunks and then reduces them).  Job order: (tile 0, chunk c), (tile 0,
+  // waiting for it (the serial form scored a tile's two chunks and then
+  // reduced them).  Job order: (tile 0, chunk c), (tile 0,
   // c + 1), (tile 1, c), ... then the next unit's (tile 0, c + 2) from the
   // rows loaded a unit ahead.
   if (c0 < uf) {
@@ -623,27 +619,11 @@ __device__ __forceinline__ void nh_sweep(const _Float16 *__restrict__ vh, int c0
     }
     unit(a, a, c, X, Y, std::false_type{});
   }
-#else
-  if (c0 < uf) {
-    nh8 a[4], p[4];
-    load(c0, a);
-    for (int c = c0; c < uf; c += 2) {
-      if (c + 2 < uf) load(c + 2, p);
-#pragma unroll
-      for (int u = 0; u < NT; u++) {
-        t[u].insert(unit_min(u, c, a, std::false_type{}), c >> 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++) a[k] = p[k];
-    }
-  }
-#endif
   if (uf < c1) {  // the last unit: a lone chunk and/or rows past the tree's end
     nh8 a[4];
     load(uf, a);  // the row arrays hold whole units
 #pragma unroll
-    for (int u = 0; u < NT; u++) t[u].insert(unit_min(u, uf, a, std::true_type{}), uf >> 1);
+    for (int u = 0; u < NT; u++) t[u].insert(unit_min(u, uf, a), uf >> 1);
   }
 }
 
@@ -1641,23 +1621,6 @@ __device__ bool wave_pair_check(const TerrainView<ZT> &T, const double *s_in, co
       ok = is_valid_state<ZT, CM>(T, sc, stage_phase(stg), acc);
     }
     const unsigned long long okm = __ballot(ok), hasm = __ballot(has);
-#ifdef GBP_SEQ_REPLAY
-    // A/B arm: the samples replayed one at a time
-    for (int j = 0; j < WAVE; j++) {
-      if (!((hasm >> j) & 1ull)) break;
-      const uint32_t fj = __shfl(acc.flags, j), gj = __shfl(acc.G, j);
-      const bool okj = (okm >> j) & 1ull;
-      L.acc.G += gj;
-      L.acc.flags |= fj;
-      if (fj & GBP_F_LIMIT) {
-        decided = true;
-        break;
-      }
-      L.acc.V += 1;
-      decided = transition<ADAPTIVE>(L, okj);
-      if (decided || !okj) break;
-    }
-#else
     // The replay in parallel.  hasm is a prefix of the lanes (a lane past a
     // deciding sample has none); the run [0, j0) of passing samples ends at
     // the first failing or LIMIT one.  Each lane of the run applies its own
@@ -1720,7 +1683,6 @@ __device__ bool wave_pair_check(const TerrainView<ZT> &T, const double *s_in, co
         decided = transition<ADAPTIVE>(L, ((okm >> j0) & 1ull) != 0);
       }
     }
-#endif
   }
   uint32_t f = L.f | L.acc.flags;
   if (L.snew_kind != SN_NONE) {
