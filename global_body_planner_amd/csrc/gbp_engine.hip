@@ -1107,50 +1107,13 @@ bool affine_fit(const double *d, int n, double *a, double *h, int *base) {
 // host-pointer entry points: one synchronous staging round trip through the
 // handle's workspace on its private stream (used by the C++ adapters that
 // re-export the reference API).  An entry point states its device arrays once,
-// as a list of take calls; the list runs twice: against a null base (sizing
-// mode: only `off` advances) for the byte count the buffer is allocated with,
-// then against that buffer, which it may not outgrow.
-struct Stage {
-  char *base = nullptr;  // null: the sizing pass
-  size_t cap = 0, off = 0;
-  template <class T>
-  void take(T *&p, size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    p = base && off + count * sizeof(T) <= cap ? (T *)(base + off) : nullptr;
-    off += count * sizeof(T);
-  }
-};
-template <class F>
-size_t stage_bytes_of(F &carve) {
-  Stage S;
-  carve(S);
-  return S.off;
-}
-template <class F>
-int stage_carve(void *buf, size_t cap, F &carve) {
-  Stage S{(char *)buf, cap};
-  carve(S);
-  return S.off <= cap ? GBP_OK : GBP_E_ALLOC;
-}
-// the list carved from the handle's workspace, grown first if it is smaller
+// as a list of take calls (Stage, gbp_internal.h, shared with gbp_plan.hip);
+// here the list is carved from the handle's workspace, grown first if it is
+// smaller
 template <class F>
 int stage_ws(gbp_terrain *t, F carve) {
   const int rc = ensure_ws(&t->ws, &t->ws_bytes, stage_bytes_of(carve));
   return rc ? rc : stage_carve(t->ws, t->ws_bytes, carve);
-}
-// the list carved from a device buffer of its own, freed at scope exit (the
-// entry points without a terrain handle)
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-template <class F>
-int stage_buf(DevBuf &b, F carve) {
-  const size_t need = stage_bytes_of(carve);
-  if (hipMalloc(&b.p, need) != hipSuccess) return GBP_E_ALLOC;
-  return stage_carve(b.p, need, carve);
 }
 
 }  // namespace

@@ -130,6 +130,53 @@ inline int ensure_ws(void **ws, size_t *have, size_t need) {
   return GBP_OK;
 }
 
+// Device arrays stated once, as a list of take calls (a callable over a
+// Stage &), 256-byte aligned in the order written.  The list runs twice:
+// against a null base (the sizing pass: only `off` advances) for the byte
+// count the buffer is allocated with, then against that buffer, which it may
+// not outgrow (a take past `cap` yields null and stage_carve reports it).
+struct Stage {
+  char *base = nullptr;  // null: the sizing pass
+  size_t cap = 0, off = 0;
+  template <class T>
+  void take(T *&p, size_t count) {
+    off = (off + 255) & ~(size_t)255;
+    p = base && off + count * sizeof(T) <= cap ? (T *)(base + off) : nullptr;
+    off += count * sizeof(T);
+  }
+};
+template <class F>
+size_t stage_bytes_of(F &carve) {
+  Stage S;
+  carve(S);
+  return S.off;
+}
+template <class F>
+int stage_carve(void *buf, size_t cap, F &carve) {
+  Stage S{(char *)buf, cap};
+  carve(S);
+  return S.off <= cap ? GBP_OK : GBP_E_ALLOC;
+}
+// the list carved from a device buffer of its own, freed at scope exit
+struct DevBuf {
+  void *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+};
+template <class F>
+int stage_buf(DevBuf &b, F carve) {
+  const size_t need = stage_bytes_of(carve);
+  if (hipMalloc(&b.p, need) != hipSuccess) {
+    b.p = nullptr;
+    return GBP_E_ALLOC;
+  }
+  return stage_carve(b.p, need, carve);
+}
+
 // the device's look-ahead stream of the planner loop (created once per
 // process and device; null on failure); gbp_plan.hip
 hipStream_t gbp_internal_la_stream(int device, int num_cus);

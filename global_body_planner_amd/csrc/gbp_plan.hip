@@ -2558,12 +2558,6 @@ __global__ void k_extend_out(const gbp_plan_status *st, int64_t n, const int32_t
   }
 }
 
-#define HIPCHK_P(expr)                        \
-  do {                                        \
-    hipError_t e_ = (expr);                   \
-    if (e_ != hipSuccess) return GBP_E_HIP;   \
-  } while (0)
-
 bool tree_ok(const gbp_tree *t) { return t && t->v && t->count; }
 
 // the target set of half `half` (its parity)
@@ -2585,20 +2579,34 @@ uint32_t next_epoch(gbp_plan_ws *w) {
 
 unsigned tiles_for(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + CB - 1) / CB); }
 
-// qh: the queries' fp16 rows (nn_put_hrow layout, same offsets as q), or
-// null (converted in the search); prep: the extends' candidates are drawn
-// inside the search (returns *prepped); side: the look-ahead search's launch
-// (its own partial slots, never gated, the tree's snapshot count)
 struct NnSide {
   const int32_t *nv;   // the searched tree's vertex count at the snapshot
   const uint32_t *go;  // 0: idle
 };
+// what a search asks for beyond its queries and its tree (the default: the
+// matrix-core search of fp64 queries, nothing drawn beside it)
+template <class ZT = float>
+struct NnOpts {
+  const _Float16 *qh = nullptr;      // the queries' fp16 rows (nn_put_hrow layout, same offsets
+                                     // as q); null: converted in the search
+  const NhPrep<ZT> *prep = nullptr;  // the extends' candidates are drawn inside the search ...
+  double *cs = nullptr;              // ... and their s_near written by the reduce
+  bool *prepped = nullptr;           // out: the candidates were drawn (prep was taken)
+  const NnSide *side = nullptr;      // the look-ahead search's launch: its own partial slots,
+                                     // never gated, the tree's snapshot count
+  bool small = false;                // up to NS_MAXQ queries take the direct fp64 search
+  bool small_any = false;            // ... and any count, when its partials hold a whole batch
+};
 template <class ZT = float>
 int nn_launch(gbp_plan_ws *w, const int32_t *nq_dev, const double *q, const int32_t *q_off_dev,
               const gbp_tree *tr, int32_t *out, int num_cus, hipStream_t s,
-              const _Float16 *qh = nullptr, const NhPrep<ZT> *prep = nullptr,
-              double *cs = nullptr, bool *prepped = nullptr, const NnSide *side = nullptr,
-              bool small = false, bool small_any = false) {
+              const NnOpts<ZT> &opt = NnOpts<ZT>{}) {
+  const _Float16 *qh = opt.qh;
+  const NhPrep<ZT> *prep = opt.prep;
+  double *cs = opt.cs;
+  bool *prepped = opt.prepped;
+  const NnSide *side = opt.side;
+  const bool small = opt.small, small_any = opt.small_any;
   if (prepped) *prepped = false;
   // small: up to NS_MAXQ queries take the direct fp64 search (k_nn_small),
   // the matrix-core pair then returns at once (the count is on the device)
@@ -2688,18 +2696,25 @@ NhDraw la_draw(gbp_plan_ws *w, int32_t h, int64_t batch, const LaHalf &L) {
 // caller's stream holds so far; X: the tree h1 extends
 int la_launch(gbp_terrain *t, gbp_plan_ws *w, const gbp_tree *X, int32_t h1, int64_t batch,
               uint64_t seed, const LaHalf &L, hipStream_t s) {
-  HIPCHK_P(hipEventRecord(w->la_go, s));
-  HIPCHK_P(hipStreamWaitEvent(w->la_stream, w->la_go, 0));
+  HIPCHK(hipEventRecord(w->la_go, s));
+  HIPCHK(hipStreamWaitEvent(w->la_stream, w->la_go, 0));
   const int slot = h1 % 3, p = h1 & 1;
   const auto &set = w->tset[slot];
   NhPrep<float> prep{view<float>(t), seed, w->cap[p], t->sampling,
                      (h1 & 1) ? GBP_REVERSE : GBP_FORWARD, 0, NhDraw{}, &w->la->nt[slot]};
   if (L.draw_after) prep.dr = la_draw(w, h1 + 1, batch, L);
   const NnSide side{&w->la->nv[p], &w->la->go[p]};
+  // the look-ahead search: the set's fp16 rows, the candidates drawn inside,
+  // the side slots and X's snapshot
+  NnOpts<float> opt;
+  opt.qh = set.tqh;
+  opt.prep = &prep;
+  opt.cs = w->csp[p];
+  opt.side = &side;
   int rc = nn_launch<float>(w, &w->la->nt[slot], set.targets, nullptr, X, w->nnp[p], t->num_cus,
-                            w->la_stream, set.tqh, &prep, w->csp[p], nullptr, &side);
+                            w->la_stream, opt);
   if (rc) return rc;
-  HIPCHK_P(hipEventRecord(w->la_done, w->la_stream));
+  HIPCHK(hipEventRecord(w->la_done, w->la_stream));
   return GBP_OK;
 }
 
@@ -2737,6 +2752,20 @@ gbp_plan_ws::TimedHalf *timing_slot(gbp_plan_ws *w) {
   return h;
 }
 
+// the <ADAPTIVE, CM> instantiation of k_connect / k_star_check for the run's
+// (adaptive, cm): f(bool_constant<AD>, integral_constant<int, CM>), CM 2 (the
+// verified affine coordinates) or 0 — those four and no others
+template <class F>
+void with_adaptive_cm(bool adaptive, int cm, F f) {
+  using CM0 = std::integral_constant<int, 0>;
+  using CM2 = std::integral_constant<int, 2>;
+  if (adaptive) {
+    if (cm == 2) f(std::true_type{}, CM2{}); else f(std::true_type{}, CM0{});
+  } else {
+    if (cm == 2) f(std::false_type{}, CM2{}); else f(std::false_type{}, CM0{});
+  }
+}
+
 template <class ZT>
 int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int32_t half,
                    int direction, int64_t batch, uint64_t seed, uint64_t target_stream,
@@ -2758,12 +2787,12 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
   if (th) {
     th->star = w->star != 0;
     th->half = half;
-    HIPCHK_P(hipEventRecord(th->ev[0], s));
+    HIPCHK(hipEventRecord(th->ev[0], s));
   }
   if (searched && (!std::is_same_v<ZT, float> || t->sampling.state_flag || t->sampling.action_flag))
     return GBP_E_INVALID_ARG;
   if (searched) {
-    HIPCHK_P(hipStreamWaitEvent(s, w->la_done, 0));
+    HIPCHK(hipStreamWaitEvent(s, w->la_done, 0));
     hipLaunchKernelGGL(k_la_commit, dim3(grid_for(batch, TB, cus * 4)), dim3(TB), 0, s, st, w->la, half,
                        w->targets, T->v, T->count, w->nn, w->cs, O->count, ++w->seq);
     if (la->launch_next) {
@@ -2797,9 +2826,16 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
     }
     bool prepped = searched;
     int rc = GBP_OK;
-    if (!searched)
-      rc = nn_launch<ZT>(w, &st->n_targets, w->targets, nullptr, T, w->nn, cus, s, w->tqh,
-                         early ? &prep : nullptr, w->cs, &prepped);
+    if (!searched) {
+      // the extends' search: the targets' fp16 rows, the candidates drawn
+      // inside when they may be
+      NnOpts<ZT> opt;
+      opt.qh = w->tqh;
+      opt.prep = early ? &prep : nullptr;
+      opt.cs = w->cs;
+      opt.prepped = &prepped;
+      rc = nn_launch<ZT>(w, &st->n_targets, w->targets, nullptr, T, w->nn, cus, s, opt);
+    }
     if (!rc && launch) rc = la_launch(t, w, O, half + 1, batch, seed, *la, s);
     if (rc) return rc;
     const int64_t mmax = batch * GBP_NUM_GEN_STATES;
@@ -2819,7 +2855,7 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
                        w->esn, w->ean, T->v, T->vh, T->hm, T->a, T->g, T->parent, T->count, w->evtx,
                        w->tiles,
                        next_epoch(w), half, T->cap, ++w->seq, T->child, T->sibling, T->prev, w->star);
-  if (th) HIPCHK_P(hipEventRecord(th->ev[1], s));
+  if (th) HIPCHK(hipEventRecord(th->ev[1], s));
   const int kT = direction == GBP_FORWARD ? 0 : 1;  // T's tree index (Ta 0, Tb 1)
   gbp_plan_ws::StarSet &S = w->ss[half & 1];
   if (w->star && run(6)) {
@@ -2834,32 +2870,28 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
                        half, ++w->seq);
     hipLaunchKernelGGL(k_star_fill, dim3(gk), dim3(RB), 0, s, st, T->v, w->star_delta, S.sioff,
                        S.snb, S.sown, w->star_items, w->star_ch, ++w->seq);
-    if (th) HIPCHK_P(hipEventRecord(th->ev[6], s));
+    if (th) HIPCHK(hipEventRecord(th->ev[6], s));
     const int64_t rmax = 2 * w->star_max_pairs;  // connect checks, one wave each
     const int cm = (t->opt_affine && t->affine) ? 2 : 0;
     unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cus * GBP_STAR_GC, (rmax + 3) / 4));
     if (w->star_grid > 0) g = std::min<unsigned>(g, (unsigned)w->star_grid);  // (tests: several checks a wave)
     const uint64_t cseq = ++w->seq;
-#define GBP_SC(AD, CM)                                                                        \
-  hipLaunchKernelGGL((k_star_check<ZT, AD, CM>), dim3(g), dim3(TB), 0, s, V, st, direction, T->v, \
-                     S.snb, S.sown, S.srowof, S.srs, S.sra, S.srf, half, cseq)
-    if (adaptive) {
-      if (cm == 2) GBP_SC(true, 2); else GBP_SC(true, 0);
-    } else {
-      if (cm == 2) GBP_SC(false, 2); else GBP_SC(false, 0);
-    }
-#undef GBP_SC
-    if (th) HIPCHK_P(hipEventRecord(th->ev[7], s));
-    if (th) HIPCHK_P(hipEventRecord(th->ev[2], s));
+    with_adaptive_cm(adaptive, cm, [&](auto ad, auto c) {
+      hipLaunchKernelGGL((k_star_check<ZT, decltype(ad)::value, decltype(c)::value>), dim3(g), dim3(TB),
+                         0, s, V, st, direction, T->v, S.snb, S.sown, S.srowof, S.srs, S.sra, S.srf,
+                         half, cseq);
+    });
+    if (th) HIPCHK(hipEventRecord(th->ev[7], s));
+    if (th) HIPCHK(hipEventRecord(th->ev[2], s));
   }
   if (w->star && run(7)) {
     // stage 7, the ordered replay, on star_stream: it changes T's parents, g
     // and successor lists only, which nothing reads before half h + 1's
     // stage 5 (its appends into T wait for it: rdone[kT]); the connects of
     // this half and the next half's extends of O run beside it
-    HIPCHK_P(hipEventRecord(w->star_e6, s));
-    HIPCHK_P(hipStreamWaitEvent(w->star_stream, w->star_e6, 0));
-    if (th) HIPCHK_P(hipEventRecord(th->ev[3], w->star_stream));
+    HIPCHK(hipEventRecord(w->star_e6, s));
+    HIPCHK(hipStreamWaitEvent(w->star_stream, w->star_e6, 0));
+    if (th) HIPCHK(hipEventRecord(th->ev[3], w->star_stream));
     StarLds lds;
     if (w->star_lds[0] >= 0) {
       lds.rp = w->star_lds[0];
@@ -2869,31 +2901,30 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
     hipLaunchKernelGGL(k_star_replay, dim3(1), dim3(RW), 0, w->star_stream, st, T->v, T->a, T->g,
                        T->parent, T->child, T->sibling, T->prev, S.soff, S.snb, S.sown, S.srowof,
                        S.sra, S.srf, S.meta, T->bfs, T->bfs + T->cap, T->count, lds, ++w->seq);
-    HIPCHK_P(hipEventRecord(w->star_rdone[kT], w->star_stream));
+    HIPCHK(hipEventRecord(w->star_rdone[kT], w->star_stream));
   }
   if (!O) return hipGetLastError() == hipSuccess ? GBP_OK : GBP_E_HIP;
   const int cdir = direction == GBP_FORWARD ? GBP_REVERSE : GBP_FORWARD;
   if (run(4)) {
     // queries: T's new vertices, rows [added_base, added_base + n_added)
-    int rc = nn_launch<float>(w, &st->n_added, T->v, &st->added_base, O, w->nno, cus, s, T->vh, nullptr,
-                       nullptr, nullptr, nullptr, true, true);
+    // the connects' search: T's fp16 rows, the direct search for any count
+    NnOpts<float> opt;
+    opt.qh = T->vh;
+    opt.small = opt.small_any = true;
+    int rc = nn_launch<float>(w, &st->n_added, T->v, &st->added_base, O, w->nno, cus, s, opt);
     if (rc) return rc;
     const int cm = (t->opt_affine && t->affine) ? 2 : 0;
     const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cus * GBP_CONNECT_GC, (batch + 3) / 4));
     const uint64_t kseq = ++w->seq;
-#define GBP_KC(AD, CM)                                                                         \
-  hipLaunchKernelGGL((k_connect<ZT, AD, CM>), dim3(g), dim3(TB), 0, s, V, st, cdir, T->v, O->v, \
-                     w->nno, w->kres, w->ksn, w->kan, w->kf, half, kseq)
-    if (adaptive) {
-      if (cm == 2) GBP_KC(true, 2); else GBP_KC(true, 0);
-    } else {
-      if (cm == 2) GBP_KC(false, 2); else GBP_KC(false, 0);
-    }
-#undef GBP_KC
+    with_adaptive_cm(adaptive, cm, [&](auto ad, auto c) {
+      hipLaunchKernelGGL((k_connect<ZT, decltype(ad)::value, decltype(c)::value>), dim3(g), dim3(TB), 0,
+                         s, V, st, cdir, T->v, O->v, w->nno, w->kres, w->ksn, w->kan, w->kf, half,
+                         kseq);
+    });
   }
   if (run(5)) {
     // O's last replay (half h - 1's, on star_stream) before appending into O
-    if (w->star) HIPCHK_P(hipStreamWaitEvent(s, w->star_rdone[1 - kT], 0));
+    if (w->star) HIPCHK(hipStreamWaitEvent(s, w->star_rdone[1 - kT], 0));
     const bool t_is_a = direction == GBP_FORWARD;
     StarShared ssh;
     if (w->star) {  // the REACHED connections kept, listed by the append itself
@@ -2915,20 +2946,42 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
         // on star_stream behind this half's replay (Tb's g final) and half h - 1's
         // (Ta's); the next replay of Ta queues behind it, and half h + 1's
         // appends into Tb wait for it (rdone[kT] moves past it)
-        HIPCHK_P(hipEventRecord(w->star_e5, s));
-        HIPCHK_P(hipStreamWaitEvent(w->star_stream, w->star_e5, 0));
+        HIPCHK(hipEventRecord(w->star_e5, s));
+        HIPCHK(hipStreamWaitEvent(w->star_stream, w->star_e5, 0));
         hipLaunchKernelGGL(k_star_rank, dim3(1), dim3(RB), 0, w->star_stream, st, w->sshared, S.meta,
                            t_is_a ? T->g : O->g, t_is_a ? O->g : T->g, ++w->seq);
-        HIPCHK_P(hipEventRecord(w->star_rdone[kT], w->star_stream));
+        HIPCHK(hipEventRecord(w->star_rdone[kT], w->star_stream));
       }
     }
   }
   if (th) {
-    if (th->star) HIPCHK_P(hipEventRecord(th->ev[4], w->star_stream));
-    HIPCHK_P(hipEventRecord(th->ev[5], s));
+    if (th->star) HIPCHK(hipEventRecord(th->ev[4], w->star_stream));
+    HIPCHK(hipEventRecord(th->ev[5], s));
     th->pending = true;
   }
   return hipGetLastError() == hipSuccess ? GBP_OK : GBP_E_HIP;
+}
+
+// enqueue_stages for the terrain's height storage
+template <class... Args>
+int enqueue_stages_of(gbp_terrain *t, Args... args) {
+  return t->storage == GBP_STORAGE_F32 ? enqueue_stages<float>(t, args...)
+                                       : enqueue_stages<double>(t, args...);
+}
+
+// the end of a planner call: nothing of it stays on la_stream or star_stream
+// past the caller's stream (a host that reads the status, reserves or
+// destroys after the call sees it finished).  la_done already follows the
+// call's last look-ahead launch (re-recording it on the device-wide la_stream
+// would also wait for other workspaces' searches: ADVICE r05); the replay and
+// the ranking on star_stream end before the caller's stream goes on
+int join_side_streams(gbp_plan_ws *w, hipStream_t s, bool la_used) {
+  if (la_used) HIPCHK(hipStreamWaitEvent(s, w->la_done, 0));
+  if (w->star) {
+    HIPCHK(hipEventRecord(w->star_sdone, w->star_stream));
+    HIPCHK(hipStreamWaitEvent(s, w->star_sdone, 0));
+  }
+  return GBP_OK;
 }
 
 }  // namespace
@@ -2938,62 +2991,102 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
 // ============================================================================
 namespace {
 
-struct Guard {
-  int prev = -1;
-  explicit Guard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~Guard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
+// The tree's capacity-sized allocations, stated once, in allocation order;
+// tree_alloc, gbp_tree_reserve's copies and frees and gbp_tree_destroy all go
+// through this list (count and hm are gbp_tree_create's and
+// gbp_tree_destroy's own).  An allocation holds `parts` sub-arrays of
+// [capacity] rows back to back, so a sub-array's offset depends on the
+// capacity; a reserve carries the first `copied` of them over, the rest is
+// scratch.
+struct TreeArray {
+  size_t row;         // bytes per vertex of one sub-array
+  int parts = 1;
+  int copied = 1;
+  int64_t round = 1;  // rows allocated: the capacity rounded up to a multiple
+  size_t bytes(int64_t cap) const { return row * parts * (size_t)((cap + round - 1) / round * round); }
+  size_t part_offset(int k, int64_t cap) const { return row * k * (size_t)cap; }
 };
-
-template <class T>
-T *carve(char *&p, size_t count) {
-  p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-  T *r = (T *)p;
-  p += count * sizeof(T);
-  return r;
+template <class F>
+void for_each_tree_array(F f) {
+  f(&gbp_tree::v, TreeArray{64});
+  f(&gbp_tree::a, TreeArray{80});
+  f(&gbp_tree::g, TreeArray{8});
+  f(&gbp_tree::parent, TreeArray{4});
+  // child | sibling | prev | bfs[2]: the successor lists survive a reserve,
+  // the subtree update's two level queues are scratch
+  f(&gbp_tree::child, TreeArray{4, 5, 3});
+  // the fp16 rows in whole 64-row units (nh_sweep loads a unit's rows past the
+  // tree's end and masks their scores)
+  f(&gbp_tree::vh, TreeArray{2 * NH_ROW, 1, 1, 64});
 }
 
+void tree_free_arrays(gbp_tree *t) {
+  for_each_tree_array([&](auto m, const TreeArray &) {
+    if (t->*m) (void)hipFree(t->*m);
+    t->*m = nullptr;
+  });
+}
+
+// fresh arrays of `cap` rows in *t (what it held before is the caller's to
+// free); on failure nothing is allocated and *t is unchanged
 int tree_alloc(gbp_tree *t, int64_t cap) {
-  double *v = nullptr, *a = nullptr, *g = nullptr;
-  _Float16 *vh = nullptr;
-  int32_t *p = nullptr, *ch = nullptr;
-  if (hipMalloc(&v, 64 * cap) != hipSuccess) return GBP_E_ALLOC;
-  if (hipMalloc(&a, 80 * cap) != hipSuccess || hipMalloc(&g, 8 * cap) != hipSuccess ||
-      hipMalloc(&p, 4 * cap) != hipSuccess || hipMalloc(&ch, 20 * cap) != hipSuccess ||
-      hipMalloc(&vh, 2 * NH_ROW * ((cap + 63) & ~(int64_t)63)) != hipSuccess) {
-    (void)hipFree(v);
-    if (a) (void)hipFree(a);
-    if (g) (void)hipFree(g);
-    if (p) (void)hipFree(p);
-    if (ch) (void)hipFree(ch);
+  gbp_tree n = *t;
+  for_each_tree_array([&](auto m, const TreeArray &) { n.*m = nullptr; });
+  bool ok = true;
+  for_each_tree_array([&](auto m, const TreeArray &A) {
+    if (ok && hipMalloc(&(n.*m), A.bytes(cap)) != hipSuccess) {
+      n.*m = nullptr;
+      ok = false;
+    }
+  });
+  if (!ok) {
+    tree_free_arrays(&n);
     return GBP_E_ALLOC;
   }
-  t->v = v;
-  t->vh = vh;
-  t->a = a;
-  t->g = g;
-  t->parent = p;
-  t->child = ch;  // [cap] first children, [cap] next / [cap] previous siblings, [2 cap] queues
-  t->sibling = ch + cap;
-  t->prev = ch + 2 * cap;
-  t->bfs = ch + 3 * cap;
-  t->cap = cap;
+  n.sibling = n.child + cap;
+  n.prev = n.child + 2 * cap;
+  n.bfs = n.child + 3 * cap;
+  n.cap = cap;
+  *t = n;
   return GBP_OK;
 }
 
 template <class T>
 int d2h(T *dst, const T *src, size_t count, hipStream_t s) {
-  HIPCHK_P(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, s));
   return GBP_OK;
 }
 template <class T>
 int h2d(T *dst, const T *src, size_t count, hipStream_t s) {
-  HIPCHK_P(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, s));
   return GBP_OK;
+}
+
+// gbp_tree_append_host / gbp_tree_load_host after their validation: the tree
+// raised to `capacity` rows, the n host rows staged through a buffer of their
+// own and written by `kernel` (k_tree_append / k_tree_load); synchronous
+using TreeRowsKernel = void (*)(gbp_tree, int64_t, const double *, const double *, const int32_t *);
+int tree_put_rows(gbp_tree *t, int64_t capacity, TreeRowsKernel kernel, int64_t n,
+                  const double *states, const double *actions, const int32_t *parents,
+                  gbp_stream stream) {
+  int rc = gbp_tree_reserve(t, capacity, stream);
+  if (rc) return rc;
+  DeviceGuard g(t->device);
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf buf;
+  double *ds, *da;
+  int32_t *dp;
+  rc = stage_buf(buf, [&](Stage &S) { S.take(ds, 8 * n); S.take(da, 10 * n); S.take(dp, n); });
+  if (rc) return rc;
+  rc = h2d(ds, states, 8 * n, s);
+  if (!rc) rc = h2d(da, actions, 10 * n, s);
+  if (!rc) rc = h2d(dp, parents, n, s);
+  if (!rc) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(1), 0, s, *t, n, ds, da, dp);
+    if (hipGetLastError() != hipSuccess) rc = GBP_E_HIP;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = GBP_E_HIP;
+  return rc;
 }
 
 }  // namespace
@@ -3002,15 +3095,15 @@ extern "C" {
 
 int gbp_stream_create(int device, gbp_stream *out) {
   if (!out) return GBP_E_INVALID_ARG;
-  Guard g(device);
+  DeviceGuard g(device);
   hipStream_t s = nullptr;
-  HIPCHK_P(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   *out = (gbp_stream)s;
   return GBP_OK;
 }
 
 int gbp_stream_destroy(gbp_stream stream) {
-  if (stream) HIPCHK_P(hipStreamDestroy((hipStream_t)stream));
+  if (stream) HIPCHK(hipStreamDestroy((hipStream_t)stream));
   return GBP_OK;
 }
 
@@ -3020,7 +3113,7 @@ int gbp_tree_create(int device, int64_t capacity, gbp_tree **out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
   if (device < 0 || device >= ndev) return GBP_E_INVALID_ARG;
-  Guard g(device);
+  DeviceGuard g(device);
   gbp_tree *t = new (std::nothrow) gbp_tree();
   if (!t) return GBP_E_ALLOC;
   t->device = device;
@@ -3044,11 +3137,11 @@ int gbp_tree_create(int device, int64_t capacity, gbp_tree **out) {
 
 int gbp_tree_destroy(gbp_tree *t) {
   if (!t) return GBP_E_BAD_HANDLE;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   (void)hipDeviceSynchronize();
-  void *ptrs[] = {t->v, t->vh, t->hm, t->a, t->g, t->parent, t->child, t->count};
-  for (void *p : ptrs)
-    if (p) (void)hipFree(p);
+  tree_free_arrays(t);
+  if (t->hm) (void)hipFree(t->hm);
+  if (t->count) (void)hipFree(t->count);
   delete t;
   return GBP_OK;
 }
@@ -3057,50 +3150,47 @@ int gbp_tree_reserve(gbp_tree *t, int64_t capacity, gbp_stream stream) {
   if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
   if (capacity <= t->cap) return GBP_OK;
   if (capacity > 0x7FFFFFFF) return GBP_E_SHAPE;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipStream_t s = (hipStream_t)stream;
-  HIPCHK_P(hipStreamSynchronize(s));
-  gbp_tree old = *t;
-  int rc = tree_alloc(t, capacity);
-  if (rc) {
-    *t = old;
-    return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  gbp_tree grown = *t;
+  const int rc = tree_alloc(&grown, capacity);
+  if (rc) return rc;
+  bool ok = true;
+  for_each_tree_array([&](auto m, const TreeArray &A) {
+    for (int k = 0; k < A.copied; k++)
+      ok = ok && hipMemcpyAsync((char *)(grown.*m) + A.part_offset(k, grown.cap),
+                                (const char *)(t->*m) + A.part_offset(k, t->cap), A.row * t->cap,
+                                hipMemcpyDeviceToDevice, s) == hipSuccess;
+  });
+  if (!ok || hipStreamSynchronize(s) != hipSuccess) {
+    // the tree keeps its old arrays, valid; the new ones go once no copy is in flight
+    (void)hipDeviceSynchronize();
+    tree_free_arrays(&grown);
+    return GBP_E_HIP;
   }
-  HIPCHK_P(hipMemcpyAsync(t->v, old.v, 64 * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipMemcpyAsync(t->vh, old.vh, 2 * NH_ROW * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipMemcpyAsync(t->a, old.a, 80 * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipMemcpyAsync(t->g, old.g, 8 * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipMemcpyAsync(t->parent, old.parent, 4 * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipMemcpyAsync(t->child, old.child, 4 * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipMemcpyAsync(t->sibling, old.sibling, 4 * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipMemcpyAsync(t->prev, old.prev, 4 * old.cap, hipMemcpyDeviceToDevice, s));
-  HIPCHK_P(hipStreamSynchronize(s));
-  (void)hipFree(old.v);
-  (void)hipFree(old.vh);
-  (void)hipFree(old.a);
-  (void)hipFree(old.g);
-  (void)hipFree(old.parent);
-  (void)hipFree(old.child);
+  tree_free_arrays(t);
+  *t = grown;
   return GBP_OK;
 }
 
 int gbp_tree_init(gbp_tree *t, const double *root, gbp_stream stream) {
   if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
   if (!root) return GBP_E_INVALID_ARG;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipLaunchKernelGGL(k_tree_init, dim3(1), dim3(1), 0, (hipStream_t)stream, *t, root[0], root[1],
                      root[2], root[3], root[4], root[5], root[6], root[7]);
-  HIPCHK_P(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return GBP_OK;
 }
 
 int gbp_tree_size(gbp_tree *t, int64_t *count, gbp_stream stream) {
   if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
   if (!count) return GBP_E_INVALID_ARG;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   int32_t c = 0;
-  HIPCHK_P(hipMemcpyAsync(&c, t->count, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK_P(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipMemcpyAsync(&c, t->count, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   *count = c;
   return GBP_OK;
 }
@@ -3117,7 +3207,7 @@ int gbp_tree_read(gbp_tree *t, int64_t first, int64_t n, double *states, double 
   if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
   if (first < 0 || n < 0 || first + n > t->cap) return GBP_E_INVALID_ARG;
   if (n == 0) return GBP_OK;
-  Guard gd(t->device);
+  DeviceGuard gd(t->device);
   hipStream_t s = (hipStream_t)stream;
   int rc = GBP_OK;
   if (!rc && states) rc = d2h(states, t->v + 8 * first, 8 * n, s);
@@ -3125,7 +3215,7 @@ int gbp_tree_read(gbp_tree *t, int64_t first, int64_t n, double *states, double 
   if (!rc && parents) rc = d2h(parents, t->parent + first, n, s);
   if (!rc && g) rc = d2h(g, t->g + first, n, s);
   if (rc) return rc;
-  HIPCHK_P(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(s));
   return GBP_OK;
 }
 
@@ -3139,25 +3229,8 @@ int gbp_tree_append_host(gbp_tree *t, int64_t n, const double *states, const dou
   if (rc) return rc;
   for (int64_t i = 0; i < n; i++)
     if (parents[i] < -1 || parents[i] >= c + i) return GBP_E_INVALID_ARG;
-  if (c + n > t->cap) rc = gbp_tree_reserve(t, std::max<int64_t>(2 * t->cap, c + n), stream);
-  if (rc) return rc;
-  Guard g(t->device);
-  hipStream_t s = (hipStream_t)stream;
-  void *buf = nullptr;
-  HIPCHK_P(hipMalloc(&buf, (size_t)n * (64 + 80 + 4) + 512));
-  char *p = (char *)buf;
-  double *ds = carve<double>(p, 8 * n), *da = carve<double>(p, 10 * n);
-  int32_t *dp = carve<int32_t>(p, n);
-  rc = h2d(ds, states, 8 * n, s);
-  if (!rc) rc = h2d(da, actions, 10 * n, s);
-  if (!rc) rc = h2d(dp, parents, n, s);
-  if (!rc) {
-    hipLaunchKernelGGL(k_tree_append, dim3(1), dim3(1), 0, s, *t, n, ds, da, dp);
-    if (hipGetLastError() != hipSuccess) rc = GBP_E_HIP;
-  }
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = GBP_E_HIP;
-  (void)hipFree(buf);
-  return rc;
+  const int64_t capacity = c + n > t->cap ? std::max<int64_t>(2 * t->cap, c + n) : t->cap;
+  return tree_put_rows(t, capacity, k_tree_append, n, states, actions, parents, stream);
 }
 
 int gbp_tree_load_host(gbp_tree *t, int64_t n, const double *states, const double *actions,
@@ -3179,26 +3252,7 @@ int gbp_tree_load_host(gbp_tree *t, int64_t n, const double *states, const doubl
       for (int32_t c = head[queue[h]]; c >= 0; c = next[c]) queue.push_back(c);
     if ((int64_t)queue.size() != n) return GBP_E_INVALID_ARG;
   }
-  int rc = GBP_OK;
-  if (n > t->cap) rc = gbp_tree_reserve(t, n, stream);
-  if (rc) return rc;
-  Guard g(t->device);
-  hipStream_t s = (hipStream_t)stream;
-  void *buf = nullptr;
-  HIPCHK_P(hipMalloc(&buf, (size_t)n * (64 + 80 + 4) + 512));
-  char *p = (char *)buf;
-  double *ds = carve<double>(p, 8 * n), *da = carve<double>(p, 10 * n);
-  int32_t *dp = carve<int32_t>(p, n);
-  rc = h2d(ds, states, 8 * n, s);
-  if (!rc) rc = h2d(da, actions, 10 * n, s);
-  if (!rc) rc = h2d(dp, parents, n, s);
-  if (!rc) {
-    hipLaunchKernelGGL(k_tree_load, dim3(1), dim3(1), 0, s, *t, n, ds, da, dp);
-    if (hipGetLastError() != hipSuccess) rc = GBP_E_HIP;
-  }
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = GBP_E_HIP;
-  (void)hipFree(buf);
-  return rc;
+  return tree_put_rows(t, n, k_tree_load, n, states, actions, parents, stream);
 }
 
 int gbp_tree_device_ptrs(gbp_tree *t, double **states, int32_t **count) {
@@ -3262,6 +3316,125 @@ extern "C++" __attribute__((visibility("hidden"))) hipStream_t gbp_internal_la_s
   return st;
 }
 
+// RRT*'s side stream and its events, all or none
+static void star_stream_destroy(gbp_plan_ws *w) {
+  if (w->star_stream) (void)hipStreamSynchronize(w->star_stream);
+  hipEvent_t *ev[] = {&w->star_e6, &w->star_e5, &w->star_rdone[0], &w->star_rdone[1], &w->star_sdone};
+  for (hipEvent_t *e : ev) {
+    if (*e) (void)hipEventDestroy(*e);
+    *e = nullptr;
+  }
+  if (w->star_stream) (void)hipStreamDestroy(w->star_stream);
+  w->star_stream = nullptr;
+}
+
+static int star_stream_create(gbp_plan_ws *w) {
+  // the workspace's own (a device-wide stream would make one planner's joins
+  // wait for another's replays), CU-masked to the last n/8 CUs, the ones
+  // la_stream leaves free: a masked stream has a hardware queue of its own,
+  // while a plain one shares one of the process's GPU_MAX_HW_QUEUES (4)
+  // round-robin — with the caller's stream the replay then ran in line with
+  // the connects it should overlap (config 5: 52 vs 66 M pair checks/s with
+  // 8 queues)
+  int xcc = 0;
+  if (hipDeviceGetAttribute(&xcc, hipDeviceAttributeNumberOfXccs, w->device) != hipSuccess) xcc = 0;
+  const int n = w->num_cus, lo = xcc >= 2 ? n - n / xcc : n;
+  std::vector<uint32_t> mask((n + 31) / 32, 0u);
+  for (int c = lo; c < n; c++) mask[c / 32] |= 1u << (c % 32);
+  const hipError_t e = (lo > 0 && lo < n)
+                           ? hipExtStreamCreateWithCUMask(&w->star_stream, (uint32_t)mask.size(),
+                                                          mask.data())
+                           : hipStreamCreateWithFlags(&w->star_stream, hipStreamNonBlocking);
+  if (e != hipSuccess) w->star_stream = nullptr;
+  if (e != hipSuccess ||
+      hipEventCreateWithFlags(&w->star_e6, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&w->star_e5, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&w->star_rdone[0], hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&w->star_rdone[1], hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&w->star_sdone, hipEventDisableTiming) != hipSuccess) {
+    star_stream_destroy(w);
+    return GBP_E_HIP;
+  }
+  return GBP_OK;
+}
+
+// the RRT* block released and its limits forgotten: RRT* is off and the next
+// gbp_plan_star_config allocates afresh
+static void star_block_drop(gbp_plan_ws *w) {
+  if (w->star_block) (void)hipFree(w->star_block);
+  w->star_block = nullptr;
+  w->star = 0;
+  w->star_max_pairs = w->star_max_shared = 0;
+}
+
+// the RRT* block for these limits: allocated by its own list, its counters
+// zeroed, the kept connections of a smaller block (keep_shared) put back, the
+// side stream created with the first one.  Fails as a unit: the caller drops
+// the block on any error.
+static int star_block_create(gbp_plan_ws *w, int64_t max_pairs, int64_t max_shared,
+                             const std::vector<int32_t> &keep_shared) {
+  const int64_t b = w->bmax, r = 2 * max_pairs;
+  int64_t items = std::max<int64_t>(4 * b, 1 << 15);
+  // (tests: GBP_STAR_ITEMS, at least the batch, and GBP_STAR_CH small grow
+  // the chunks; GBP_STAR_GRID makes every count / fill workgroup take
+  // several items)
+  const char *ie = getenv("GBP_STAR_ITEMS");
+  if (ie && *ie) items = std::max<int64_t>(b, atoll(ie));
+  const char *le = getenv("GBP_STAR_LDS");
+  if (le && *le) {
+    int a = RP, b2 = RK, c = RQ;
+    if (sscanf(le, "%d,%d,%d", &a, &b2, &c) == 3) {
+      w->star_lds[0] = std::max(0, std::min(a, RP));
+      w->star_lds[1] = std::max(0, std::min(b2, RK));
+      w->star_lds[2] = std::max(1, std::min(c, RQ));
+    }
+  }
+  const char *ce = getenv("GBP_STAR_CH");
+  w->star_ch = ce && *ce ? std::max<int64_t>(1, atoll(ce)) : STAR_CH;
+  const char *ge = getenv("GBP_STAR_GRID");
+  w->star_grid = ge && *ge ? std::max(1, atoi(ge)) : 0;
+  w->star_items = items;
+  // the block's arrays, in order; the list sizes the allocation (Stage)
+  auto arrays = [w, b, r, items, max_pairs, max_shared](Stage &S) {
+    for (auto &ss : w->ss) {
+      S.take(ss.scnt, items);
+      S.take(ss.sioff, items);
+      S.take(ss.soff, b + 1);
+      S.take(ss.snb, max_pairs);
+      S.take(ss.sown, max_pairs);
+      S.take(ss.srowof, r);
+      S.take(ss.srs, 8 * r);
+      S.take(ss.sra, 10 * r);
+      S.take(ss.srf, r);
+      S.take(ss.meta, 4);
+      S.take(ss.sfin, 64);
+    }
+    // the last arrays of the block: kvtx written at a connection's index
+    // < bmax (k_append), sshared at pairs < max_shared (k_append, k_star_rank),
+    // element by element, so nothing pads them
+    S.take(w->kvtx, b);
+    S.take(w->sshared, 2 * max_shared);
+  };
+  const size_t bytes = stage_bytes_of(arrays);
+  if (hipMalloc(&w->star_block, bytes) != hipSuccess) {
+    w->star_block = nullptr;
+    return GBP_E_ALLOC;
+  }
+  int rc = stage_carve(w->star_block, bytes, arrays);
+  if (!rc && !w->star_stream) rc = star_stream_create(w);
+  if (rc) return rc;
+  for (auto &ss : w->ss)  // (epoch 0 is never a launch's: seq starts at 1)
+    if (hipMemset(ss.sfin, 0, 4 * 64) != hipSuccess ||
+        hipMemset(ss.scnt, 0, 8 * (size_t)items) != hipSuccess)
+      return GBP_E_HIP;
+  if (!keep_shared.empty() &&
+      hipMemcpy(w->sshared, keep_shared.data(), 4 * keep_shared.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return GBP_E_HIP;
+  w->star_max_pairs = max_pairs;
+  w->star_max_shared = max_shared;
+  return GBP_OK;
+}
+
 static void ws_free(gbp_plan_ws *w) {
   if (w->ntring) {
     (void)hipDeviceSynchronize();
@@ -3272,13 +3445,7 @@ static void ws_free(gbp_plan_ws *w) {
   }
   if (w->la_go) (void)hipEventDestroy(w->la_go);
   if (w->la_done) (void)hipEventDestroy(w->la_done);
-  if (w->star_stream) {
-    (void)hipStreamSynchronize(w->star_stream);
-    hipEvent_t ev[] = {w->star_e6, w->star_e5, w->star_rdone[0], w->star_rdone[1], w->star_sdone};
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    (void)hipStreamDestroy(w->star_stream);
-  }
+  star_stream_destroy(w);
   if (w->block) (void)hipFree(w->block);
   if (w->star_block) (void)hipFree(w->star_block);
   delete w;
@@ -3288,7 +3455,7 @@ int gbp_plan_ws_create(gbp_terrain *t, int64_t max_batch, gbp_plan_ws **out) {
   if (!t || !out) return GBP_E_INVALID_ARG;
   if (max_batch < 1 || max_batch > (1 << 24)) return GBP_E_INVALID_ARG;
   *out = nullptr;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   gbp_plan_ws *w = new (std::nothrow) gbp_plan_ws();
   if (!w) return GBP_E_ALLOC;
   w->device = t->device;
@@ -3312,67 +3479,71 @@ int gbp_plan_ws_create(gbp_terrain *t, int64_t max_batch, gbp_plan_ws **out) {
     if (e && *e) w->ns_grid = std::max(1, std::min(1024, atoi(e)));
   }
   w->ns_capq = (int64_t)w->ns_grid * b <= ((int64_t)1 << 22) ? std::max<int64_t>(b, NS_MAXQ) : NS_MAXQ;
-  const size_t nsbytes = (size_t)w->ns_grid * w->ns_capq * 12 + 512;
-  const size_t bytes = nsbytes + sizeof(gbp_plan_status) + 16 * w->ntiles + 3 * (64 * b + 4 * b + 64 * b + 64 * b) +
-                       1024 + m * (2 * 64 + 2 * 80 + 64 + 4 + 4) + b * (2 * 4 + 4 + 64 + 80 + 4 + 4) +
-                       b * (4 + 4 + 64 + 80 + 4) + 2 * NN_MAX_CHUNKS * b * (16 + 16) + 64 * b + 512 +
-                       64 * 256 + 0 /* ns partials: below */ + 1024 +
-                       2 * ((size_t)NSC_CAP * 8 + (size_t)NSC_UNITS * 12 + 32 * b + 1024);
+  for (auto &sb : w->nsb) {
+    const char *cenv = getenv("GBP_NSC_CAP");  // (a small list: the fallback's test)
+    sb.cap = (uint32_t)std::max(1, std::min(NSC_CAP, cenv && *cenv ? atoi(cenv) : NSC_CAP));
+  }
+  // the block's arrays, in order; the list sizes the allocation (Stage)
+  auto arrays = [w, b, m](Stage &S) {
+    S.take(w->st, 1);
+    S.take(w->la, 1);
+    S.take(w->tiles, w->ntiles);
+    S.take(w->la_tiles, w->ntiles);
+    for (auto &ts : w->tset) {
+      S.take(ts.cand, 8 * b);
+      S.take(ts.cflag, b);
+      S.take(ts.targets, 8 * b);
+      S.take(ts.tqh, NH_ROW * b);
+    }
+    for (int k = 0; k < 2; k++) {
+      S.take(w->nnp[k], b);
+      S.take(w->csp[k], 8 * m);
+      S.take(w->cap[k], 10 * m);
+    }
+    S.take(w->csn, 8 * m);
+    S.take(w->cf, m);
+    S.take(w->cc, m);
+    S.take(w->eres, b);
+    S.take(w->echo, b);
+    S.take(w->esn, 8 * b);
+    S.take(w->ean, 10 * b);
+    S.take(w->ef, b);
+    S.take(w->evtx, b);
+    S.take(w->nno, b);
+    S.take(w->kres, b);
+    S.take(w->ksn, 8 * b);
+    S.take(w->kan, 10 * b);
+    S.take(w->kf, b);
+    S.take(w->nn_d, 2 * NN_MAX_CHUNKS * b);   // k_nn_mfma: float4 per slot
+    S.take(w->nn_i, 4 * NN_MAX_CHUNKS * b);   // k_nn_mfma: int4 per slot
+    S.take(w->nn_d2, 2 * NN_MAX_CHUNKS * b);
+    S.take(w->nn_i2, 4 * NN_MAX_CHUNKS * b);
+    S.take(w->ns_d, w->ns_grid * w->ns_capq);
+    S.take(w->ns_i, w->ns_grid * w->ns_capq);
+    S.take(w->ns_fin, 64);
+    for (auto &sb : w->nsb) {
+      S.take(sb.list, NSC_CAP);
+      S.take(sb.ed, NSC_UNITS);
+      S.take(sb.ei, NSC_UNITS);
+      S.take(sb.cnt, 64);
+      // the last arrays of the block: each read and written at a query's
+      // index < bmax only (k_nn_hreduce, k_nn_scan_merge), so nothing pads them
+      S.take(sb.hd, b);
+      S.take(sb.hi, b);
+      S.take(sb.qh, b);
+    }
+  };
+  const size_t bytes = stage_bytes_of(arrays);
   if (hipMalloc(&w->block, bytes) != hipSuccess) {
     delete w;
     return GBP_E_ALLOC;
   }
-  char *p = (char *)w->block;
-  w->st = carve<gbp_plan_status>(p, 1);
-  w->la = carve<gbp_plan_la>(p, 1);
-  w->tiles = carve<unsigned long long>(p, w->ntiles);
-  w->la_tiles = carve<unsigned long long>(p, w->ntiles);
-  for (auto &ts : w->tset) {
-    ts.cand = carve<double>(p, 8 * b);
-    ts.cflag = carve<uint32_t>(p, b);
-    ts.targets = carve<double>(p, 8 * b);
-    ts.tqh = carve<_Float16>(p, 32 * b);
-  }
-  for (int k = 0; k < 2; k++) {
-    w->nnp[k] = carve<int32_t>(p, b);
-    w->csp[k] = carve<double>(p, 8 * m);
-    w->cap[k] = carve<double>(p, 10 * m);
+  if (stage_carve(w->block, bytes, arrays) != GBP_OK) {
+    ws_free(w);
+    return GBP_E_ALLOC;
   }
   select_targets(w, 0);
-  w->csn = carve<double>(p, 8 * m);
-  w->cf = carve<uint32_t>(p, m);
-  w->cc = carve<uint32_t>(p, m);
-  w->eres = carve<int32_t>(p, b);
-  w->echo = carve<int32_t>(p, b);
-  w->esn = carve<double>(p, 8 * b);
-  w->ean = carve<double>(p, 10 * b);
-  w->ef = carve<uint32_t>(p, b);
-  w->evtx = carve<int32_t>(p, b);
-  w->nno = carve<int32_t>(p, b);
-  w->kres = carve<int32_t>(p, b);
-  w->ksn = carve<double>(p, 8 * b);
-  w->kan = carve<double>(p, 10 * b);
-  w->kf = carve<uint32_t>(p, b);
-  w->nn_d = carve<double>(p, 2 * NN_MAX_CHUNKS * b);   // k_nn_mfma: float4 per slot
-  w->nn_i = carve<int32_t>(p, 4 * NN_MAX_CHUNKS * b);  // k_nn_mfma: int4 per slot
-  w->nn_d2 = carve<double>(p, 2 * NN_MAX_CHUNKS * b);
-  w->nn_i2 = carve<int32_t>(p, 4 * NN_MAX_CHUNKS * b);
-  w->ns_d = carve<double>(p, (int64_t)w->ns_grid * w->ns_capq);
-  w->ns_i = carve<int32_t>(p, (int64_t)w->ns_grid * w->ns_capq);
-  w->ns_fin = carve<uint32_t>(p, 64);
-  for (auto &sb : w->nsb) {
-    const char *cenv = getenv("GBP_NSC_CAP");  // (a small list: the fallback's test)
-    sb.cap = (uint32_t)std::max(1, std::min(NSC_CAP, cenv && *cenv ? atoi(cenv) : NSC_CAP));
-    sb.list = carve<int2>(p, NSC_CAP);
-    sb.ed = carve<double>(p, NSC_UNITS);
-    sb.ei = carve<int32_t>(p, NSC_UNITS);
-    sb.cnt = carve<uint32_t>(p, 64);
-    sb.hd = carve<double>(p, b);
-    sb.hi = carve<int32_t>(p, b);
-    sb.qh = carve<int2>(p, b);
-  }
-  bool ok = (size_t)(p - (char *)w->block) <= bytes &&
-            hipMemset(w->ns_fin, 0, 4 * 64) == hipSuccess &&
+  bool ok = hipMemset(w->ns_fin, 0, 4 * 64) == hipSuccess &&
             hipMemset(w->nsb[0].cnt, 0, 4 * 64) == hipSuccess &&
             hipMemset(w->nsb[1].cnt, 0, 4 * 64) == hipSuccess &&
             hipMemset(w->tiles, 0, 8 * w->ntiles) == hipSuccess &&
@@ -3394,7 +3565,7 @@ int gbp_plan_ws_create(gbp_terrain *t, int64_t max_batch, gbp_plan_ws **out) {
 
 int gbp_plan_ws_destroy(gbp_plan_ws *w) {
   if (!w) return GBP_E_BAD_HANDLE;
-  Guard g(w->device);
+  DeviceGuard g(w->device);
   (void)hipDeviceSynchronize();
   ws_free(w);
   return GBP_OK;
@@ -3410,7 +3581,7 @@ int gbp_plan_star_config(gbp_plan_ws *w, int enable, double delta, int64_t max_p
   if (!(delta >= 0) || max_pairs < 1 || max_pairs > (1 << 28) || max_shared < 1 ||
       max_shared > (1 << 28))
     return GBP_E_INVALID_ARG;
-  Guard g(w->device);
+  DeviceGuard g(w->device);
   {
     const char *pe = getenv("GBP_STAR_PAIRS");  // (tests: a small first size, grown by the halts)
     if (pe && *pe && !w->star_block) max_pairs = std::max<int64_t>(1, std::min<int64_t>(max_pairs, atoll(pe)));
@@ -3427,91 +3598,13 @@ int gbp_plan_star_config(gbp_plan_ws *w, int enable, double delta, int64_t max_p
     if (hipMemcpy(keep_shared.data(), w->sshared, 8 * (size_t)w->star_max_shared,
                   hipMemcpyDeviceToHost) != hipSuccess)
       return GBP_E_HIP;
-    (void)hipFree(w->star_block);
-    w->star_block = nullptr;
+    star_block_drop(w);
   }
   if (!w->star_block) {
-    const int64_t b = w->bmax, r = 2 * max_pairs;
-    int64_t items = std::max<int64_t>(4 * b, 1 << 15);
-    // (tests: GBP_STAR_ITEMS, at least the batch, and GBP_STAR_CH small grow
-    // the chunks; GBP_STAR_GRID below makes every count / fill workgroup take
-    // several items)
-    const char *ie = getenv("GBP_STAR_ITEMS");
-    if (ie && *ie) items = std::max<int64_t>(b, atoll(ie));
-    const char *le = getenv("GBP_STAR_LDS");
-    if (le && *le) {
-      int a = RP, b2 = RK, c = RQ;
-      if (sscanf(le, "%d,%d,%d", &a, &b2, &c) == 3) {
-        w->star_lds[0] = std::max(0, std::min(a, RP));
-        w->star_lds[1] = std::max(0, std::min(b2, RK));
-        w->star_lds[2] = std::max(1, std::min(c, RQ));
-      }
-    }
-    const char *ce = getenv("GBP_STAR_CH");
-    w->star_ch = ce && *ce ? std::max<int64_t>(1, atoll(ce)) : STAR_CH;
-    const size_t bytes = 2 * (12 * items + 4 * (b + 1) + 8 * max_pairs + r * (4 + 4 + 64 + 80 + 4) +
-                              32 + 12 * 256) +
-                         4 * b + 8 * max_shared + 4 * 256;
-    if (hipMalloc(&w->star_block, bytes) != hipSuccess) {
-      w->star_block = nullptr;
-      w->star = 0;
-      return GBP_E_ALLOC;
-    }
-    char *p = (char *)w->star_block;
-    for (auto &S : w->ss) {
-      S.scnt = carve<unsigned long long>(p, items);
-      S.sioff = carve<int32_t>(p, items);
-      S.soff = carve<int32_t>(p, b + 1);
-      S.snb = carve<int32_t>(p, max_pairs);
-      S.sown = carve<int32_t>(p, max_pairs);
-      S.srowof = carve<int32_t>(p, r);
-      S.srs = carve<double>(p, 8 * r);
-      S.sra = carve<double>(p, 10 * r);
-      S.srf = carve<uint32_t>(p, r);
-      S.meta = carve<int64_t>(p, 4);
-      S.sfin = carve<uint32_t>(p, 64);
-    }
-    w->star_items = items;
-    const char *ge = getenv("GBP_STAR_GRID");
-    w->star_grid = ge && *ge ? std::max(1, atoi(ge)) : 0;
-    w->kvtx = carve<int32_t>(p, b);
-    w->sshared = carve<int32_t>(p, 2 * max_shared);
-    if ((size_t)(p - (char *)w->star_block) > bytes) return GBP_E_HIP;
-    for (auto &S : w->ss)  // (epoch 0 is never a launch's: seq starts at 1)
-      if (hipMemset(S.sfin, 0, 4 * 64) != hipSuccess ||
-          hipMemset(S.scnt, 0, 8 * (size_t)items) != hipSuccess)
-        return GBP_E_HIP;
-    if (!keep_shared.empty() &&
-        hipMemcpy(w->sshared, keep_shared.data(), 4 * keep_shared.size(), hipMemcpyHostToDevice) != hipSuccess)
-      return GBP_E_HIP;
-    w->star_max_pairs = max_pairs;
-    w->star_max_shared = max_shared;
-  }
-  if (!w->star_stream) {
-    // the workspace's own (a device-wide stream would make one planner's joins
-    // wait for another's replays), CU-masked to the last n/8 CUs, the ones
-    // la_stream leaves free: a masked stream has a hardware queue of its own,
-    // while a plain one shares one of the process's GPU_MAX_HW_QUEUES (4)
-    // round-robin — with the caller's stream the replay then ran in line with
-    // the connects it should overlap (config 5: 52 vs 66 M pair checks/s with
-    // 8 queues)
-    int xcc = 0;
-    if (hipDeviceGetAttribute(&xcc, hipDeviceAttributeNumberOfXccs, w->device) != hipSuccess) xcc = 0;
-    const int n = w->num_cus, lo = xcc >= 2 ? n - n / xcc : n;
-    std::vector<uint32_t> mask((n + 31) / 32, 0u);
-    for (int c = lo; c < n; c++) mask[c / 32] |= 1u << (c % 32);
-    const hipError_t e = (lo > 0 && lo < n)
-                             ? hipExtStreamCreateWithCUMask(&w->star_stream, (uint32_t)mask.size(),
-                                                            mask.data())
-                             : hipStreamCreateWithFlags(&w->star_stream, hipStreamNonBlocking);
-    if (e != hipSuccess ||
-        hipEventCreateWithFlags(&w->star_e6, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&w->star_e5, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&w->star_rdone[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&w->star_rdone[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&w->star_sdone, hipEventDisableTiming) != hipSuccess) {
-      w->star = 0;
-      return GBP_E_HIP;
+    const int rc = star_block_create(w, max_pairs, max_shared, keep_shared);
+    if (rc) {
+      star_block_drop(w);
+      return rc;
     }
   }
   w->star = 1;
@@ -3521,7 +3614,7 @@ int gbp_plan_star_config(gbp_plan_ws *w, int enable, double delta, int64_t max_p
 
 int gbp_plan_stage_timing(gbp_plan_ws *w, int enable) {
   if (!w) return GBP_E_BAD_HANDLE;
-  Guard g(w->device);
+  DeviceGuard g(w->device);
   if (enable && !w->ntring) {
     w->tring = new (std::nothrow) gbp_plan_ws::TimedHalf[256];
     if (!w->tring) return GBP_E_ALLOC;
@@ -3537,7 +3630,7 @@ int gbp_plan_stage_timing(gbp_plan_ws *w, int enable) {
 int gbp_plan_stage_times(gbp_plan_ws *w, double *us, int n, int64_t *halves, int reset) {
   if (!w) return GBP_E_BAD_HANDLE;
   if (!us || n < 5) return GBP_E_INVALID_ARG;
-  Guard g(w->device);
+  DeviceGuard g(w->device);
   timing_collect(w, false);
   for (int k = 0; k < std::min(n, 7); k++) us[k] = w->tsum[k];
   if (halves) *halves = w->tcount;
@@ -3550,19 +3643,19 @@ int gbp_plan_stage_times(gbp_plan_ws *w, double *us, int n, int64_t *halves, int
 
 int gbp_plan_reset(gbp_plan_ws *w, int64_t extend_counter, gbp_stream stream) {
   if (!w) return GBP_E_BAD_HANDLE;
-  Guard g(w->device);
+  DeviceGuard g(w->device);
   hipLaunchKernelGGL(k_plan_reset, dim3(1), dim3(1), 0, (hipStream_t)stream, w->st, extend_counter,
                      w->la);
-  HIPCHK_P(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return GBP_OK;
 }
 
 int gbp_plan_status_read(gbp_plan_ws *w, gbp_plan_status *out, gbp_stream stream) {
   if (!w) return GBP_E_BAD_HANDLE;
   if (!out) return GBP_E_INVALID_ARG;
-  Guard g(w->device);
-  HIPCHK_P(hipMemcpyAsync(out, w->st, sizeof *out, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  HIPCHK_P(hipStreamSynchronize((hipStream_t)stream));
+  DeviceGuard g(w->device);
+  HIPCHK(hipMemcpyAsync(out, w->st, sizeof *out, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
   return GBP_OK;
 }
 
@@ -3574,19 +3667,12 @@ int gbp_plan_half_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, 
   if (batch < 1 || batch > w->bmax || first_stage < 0 || first_stage > (w->star ? 7 : 5) ||
       (direction != GBP_FORWARD && direction != GBP_REVERSE) || T == O)
     return GBP_E_INVALID_ARG;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipStream_t s = (hipStream_t)stream;
-  const int rc = t->storage == GBP_STORAGE_F32
-                     ? enqueue_stages<float>(t, w, T, O, half, direction, batch, seed, target_stream,
-                                             target_index_base, adaptive, first_stage, 5, s)
-                     : enqueue_stages<double>(t, w, T, O, half, direction, batch, seed,
-                                              target_stream, target_index_base, adaptive,
-                                              first_stage, 5, s);
-  if (w->star) {  // the replay and ranking on star_stream end before the caller's stream goes on
-    HIPCHK_P(hipEventRecord(w->star_sdone, w->star_stream));
-    HIPCHK_P(hipStreamWaitEvent(s, w->star_sdone, 0));
-  }
-  return rc;
+  const int rc = enqueue_stages_of(t, w, T, O, half, direction, batch, seed, target_stream,
+                                   target_index_base, adaptive, first_stage, 5, s, nullptr);
+  const int jrc = join_side_streams(w, s, false);
+  return jrc ? jrc : rc;
 }
 
 int gbp_plan_halves_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *Ta, gbp_tree *Tb,
@@ -3597,7 +3683,7 @@ int gbp_plan_halves_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *Ta, gbp_tree *
   if (batch < 1 || batch > w->bmax || first_stage < 0 || first_stage > (w->star ? 7 : 5) ||
       n_halves < 0 || first_half < 0 || Ta == Tb)
     return GBP_E_INVALID_ARG;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipStream_t s = (hipStream_t)stream;
   // the look-ahead search (LaHalf, la_launch): half h+1's draws do not depend
   // on the trees unless the sampling is direction-biased, and its search
@@ -3630,23 +3716,12 @@ int gbp_plan_halves_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *Ta, gbp_tree *
     L.draw_after = ahead && i + 2 < n_halves;
     L.stream_a = stream_a;
     L.stream_b = stream_b;
-    rc = t->storage == GBP_STORAGE_F32
-             ? enqueue_stages<float>(t, w, T, O, h, dir, batch, seed, ts, tb, adaptive, fs, 5, s, &L)
-             : enqueue_stages<double>(t, w, T, O, h, dir, batch, seed, ts, tb, adaptive, fs, 5, s, &L);
+    rc = enqueue_stages_of(t, w, T, O, h, dir, batch, seed, ts, tb, adaptive, fs, 5, s, &L);
     searched = L.launch_next;
     used = used || L.launch_next;
   }
-  // nothing of the call stays on la_stream or star_stream past the caller's
-  // stream (a host that reads the status, reserves or destroys after this sees
-  // it finished).  la_done already follows this call's last look-ahead launch
-  // (re-recording it on the device-wide la_stream would also wait for other
-  // workspaces' searches: ADVICE r05)
-  if (used) HIPCHK_P(hipStreamWaitEvent(s, w->la_done, 0));
-  if (w->star) {
-    HIPCHK_P(hipEventRecord(w->star_sdone, w->star_stream));
-    HIPCHK_P(hipStreamWaitEvent(s, w->star_sdone, 0));
-  }
-  return rc;
+  const int jrc = join_side_streams(w, s, used);
+  return jrc ? jrc : rc;
 }
 
 int gbp_extend_tree_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, int64_t n,
@@ -3658,20 +3733,16 @@ int gbp_extend_tree_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, int64_t n,
       (direction != GBP_FORWARD && direction != GBP_REVERSE))
     return GBP_E_INVALID_ARG;
   if (n == 0) return GBP_OK;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipStream_t s = (hipStream_t)stream;
   select_targets(w, 0);
   hipLaunchKernelGGL(k_extend_setup, dim3(grid_for(8 * n, TB, t->num_cus * 4)), dim3(TB), 0, s,
                      w->st, n, n_dev, extend_base, targets, w->targets, w->tqh);
-  int rc = t->storage == GBP_STORAGE_F32
-               ? enqueue_stages<float>(t, w, T, nullptr, 0, direction, n, seed, 0, 0, adaptive, 2,
-                                       3, s)
-               : enqueue_stages<double>(t, w, T, nullptr, 0, direction, n, seed, 0, 0, adaptive, 2,
-                                        3, s);
+  int rc = enqueue_stages_of(t, w, T, nullptr, 0, direction, n, seed, 0, 0, adaptive, 2, 3, s, nullptr);
   if (rc) return rc;
   hipLaunchKernelGGL(k_extend_out, dim3(grid_for(n, TB, t->num_cus * 4)), dim3(TB), 0, s, w->st, n,
                      w->eres, w->evtx, result, new_vertex);
-  HIPCHK_P(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return GBP_OK;
 }
 
@@ -3681,15 +3752,13 @@ int gbp_extend_tree_finish_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, int6
   if (!t || !w || !tree_ok(T)) return GBP_E_BAD_HANDLE;
   if (n < 0 || n > w->bmax) return GBP_E_INVALID_ARG;
   if (n == 0) return GBP_OK;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipStream_t s = (hipStream_t)stream;
-  int rc = t->storage == GBP_STORAGE_F32
-               ? enqueue_stages<float>(t, w, T, nullptr, 0, direction, n, 0, 0, 0, 0, 3, 3, s)
-               : enqueue_stages<double>(t, w, T, nullptr, 0, direction, n, 0, 0, 0, 0, 3, 3, s);
+  int rc = enqueue_stages_of(t, w, T, nullptr, 0, direction, n, 0, 0, 0, 0, 3, 3, s, nullptr);
   if (rc) return rc;
   hipLaunchKernelGGL(k_extend_out, dim3(grid_for(n, TB, t->num_cus * 4)), dim3(TB), 0, s, w->st, n,
                      w->eres, w->evtx, result, new_vertex);
-  HIPCHK_P(hipGetLastError());
+  HIPCHK(hipGetLastError());
   return GBP_OK;
 }
 
@@ -3701,17 +3770,17 @@ int gbp_extend_tree_host(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, int64_t n,
   if (n < 0 || n > w->bmax || (n > 0 && (!targets || !result))) return GBP_E_INVALID_ARG;
   if (n_resolved) *n_resolved = 0;
   if (n == 0) return GBP_OK;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipStream_t s = t->host_stream;
   int64_t cnt = 0;
   int rc = gbp_tree_size(T, &cnt, s);
   if (!rc && cnt + n > T->cap) rc = gbp_tree_reserve(T, std::max<int64_t>(2 * T->cap, cnt + n), s);
   if (rc) return rc;
-  void *buf = nullptr;
-  HIPCHK_P(hipMalloc(&buf, (size_t)n * (64 + 8) + 512));
-  char *p = (char *)buf;
-  double *dt = carve<double>(p, 8 * n);
-  int32_t *dr = carve<int32_t>(p, n), *dv = carve<int32_t>(p, n);
+  DevBuf buf;
+  double *dt;
+  int32_t *dr, *dv;
+  rc = stage_buf(buf, [&](Stage &S) { S.take(dt, 8 * n); S.take(dr, n); S.take(dv, n); });
+  if (rc) return rc;
   rc = h2d(dt, targets, 8 * n, s);
   if (!rc) rc = gbp_plan_reset(w, 0, s);
   if (!rc)
@@ -3727,7 +3796,6 @@ int gbp_extend_tree_host(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, int64_t n,
   if (!rc) rc = d2h(result, dr, n, s);
   if (!rc && new_vertex) rc = d2h(new_vertex, dv, n, s);
   if (!rc && hipStreamSynchronize(s) != hipSuccess) rc = GBP_E_HIP;
-  (void)hipFree(buf);
   return rc;
 }
 
@@ -3736,11 +3804,157 @@ int gbp_tree_nearest_dev(gbp_plan_ws *w, gbp_tree *T, int64_t n, const double *q
   if (!w || !tree_ok(T)) return GBP_E_BAD_HANDLE;
   if (n < 0 || n > w->bmax || (n > 0 && (!queries || !index))) return GBP_E_INVALID_ARG;
   if (n == 0) return GBP_OK;
-  Guard g(w->device);
+  DeviceGuard g(w->device);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_set_queries, dim3(1), dim3(1), 0, s, w->st, (int32_t)n);
-  return nn_launch<float>(w, &w->st->n_targets, queries, nullptr, T, index, w->num_cus, s, nullptr, nullptr,
-                   nullptr, nullptr, nullptr, true);
+  // fp64 queries (rows converted in the search), the direct search for a few
+  NnOpts<float> opt;
+  opt.small = true;
+  return nn_launch<float>(w, &w->st->n_targets, queries, nullptr, T, index, w->num_cus, s, opt);
+}
+
+// gbp_plan_resolve_host's re-decisions, one per halted stage: the stage's
+// FRAGILE items decided again on the host with glibc and its outputs patched
+// on the device, item by item (a group has a handful); *k counts them
+
+// isValidState(s_rand, STANCE) of the half's draws (rrt_connect.cpp:254)
+static int resolve_targets(gbp_terrain *t, gbp_plan_ws *w, int64_t batch, hipStream_t s, int64_t *k) {
+  if (batch < 1 || batch > w->bmax) return GBP_E_INVALID_ARG;
+  int rc;
+  std::vector<uint32_t> fl(batch);
+  if ((rc = d2h(fl.data(), w->cflag, batch, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  for (int64_t i = 0; i < batch; i++) {
+    if (!(fl[i] & GBP_F_FRAGILE)) continue;
+    double q[8];
+    if ((rc = d2h(q, w->cand + 8 * i, 8, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    gbp_host::Acc acc;
+    const bool v = gbp_host::is_valid_state(t->host, q, GBP_STANCE, acc);
+    fl[i] = acc.flags | (v ? GBP_F_VALID : 0u) | GBP_F_RESOLVED;
+    if ((rc = h2d(w->cflag + i, &fl[i], 1, s))) return rc;
+    ++*k;
+  }
+  return GBP_OK;
+}
+
+// newConfig + acceptance (rrt.cpp:20-101) of every extend with a FRAGILE
+// executed candidate, on the device's own candidate actions
+static int resolve_extend(gbp_terrain *t, gbp_plan_ws *w, const gbp_tree *T, int64_t n, int direction,
+                          int adaptive, hipStream_t s, int64_t *k) {
+  int rc;
+  std::vector<uint32_t> ef(n);
+  if ((rc = d2h(ef.data(), w->ef, n, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  for (int64_t i = 0; i < n; i++) {
+    if (!(ef[i] & GBP_F_FRAGILE)) continue;
+    int32_t nn = 0;
+    double tg[8], sn0[8], act[10 * GBP_NUM_GEN_STATES];
+    if ((rc = d2h(&nn, w->nn + i, 1, s)) || (rc = d2h(tg, w->targets + 8 * i, 8, s)) ||
+        (rc = d2h(act, w->ca + 10 * GBP_NUM_GEN_STATES * i, 10 * GBP_NUM_GEN_STATES, s)))
+      return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = d2h(sn0, T->v + 8 * (int64_t)nn, 8, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const double best0 = gbp_host::state_distance(sn0, tg);
+    double best = best0, s_test[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_test = 0, s_new[8];
+    uint32_t fl = 0;
+    int found = -1;
+    for (int j = 0; j < GBP_NUM_GEN_STATES; j++) {
+      uint32_t f = 0;
+      const bool v = gbp_host::pair_check(t->host, sn0, act + 10 * j, direction, adaptive, s_test,
+                                          &t_test, &f, nullptr);
+      fl |= f & (GBP_F_VALID | GBP_F_OOD | GBP_F_NAN | GBP_F_LIMIT);
+      if (v) {
+        found = j;
+        break;
+      }
+    }
+    int32_t r = GBP_TRAPPED;
+    if (found >= 0) {
+      const double cur = gbp_host::state_distance(s_test, tg);
+      if (cur < best) {
+        best = cur;
+        memcpy(s_new, s_test, sizeof s_new);
+        r = cur <= GOAL_BOUNDS ? GBP_REACHED : GBP_ADVANCED;
+        if ((rc = h2d(w->esn + 8 * i, s_new, 8, s)) ||
+            (rc = h2d(w->ean + 10 * i, act + 10 * found, 10, s)))
+          return rc;
+      }
+    }
+    const uint32_t fr = fl | GBP_F_RESOLVED;
+    if ((rc = h2d(w->eres + i, &r, 1, s)) || (rc = h2d(w->echo + i, &found, 1, s)) ||
+        (rc = h2d(w->ef + i, &fr, 1, s)))
+      return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    ++*k;
+  }
+  return GBP_OK;
+}
+
+// RRTConnectClass::attemptConnect (rrt_connect.cpp:20-91) of every
+// connection with a FRAGILE level, recursion replayed on the host
+static int resolve_connect(gbp_terrain *t, gbp_plan_ws *w, const gbp_tree *T, const gbp_tree *O,
+                           const gbp_plan_status &st, int direction, int adaptive, hipStream_t s,
+                           int64_t *k) {
+  if (!tree_ok(O)) return GBP_E_BAD_HANDLE;
+  int rc;
+  const int64_t n = st.n_added, base = st.added_base;
+  const int cdir = direction == GBP_FORWARD ? GBP_REVERSE : GBP_FORWARD;
+  std::vector<uint32_t> kf(n);
+  if ((rc = d2h(kf.data(), w->kf, n, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  for (int64_t i = 0; i < n; i++) {
+    if (!(kf[i] & GBP_F_FRAGILE)) continue;
+    int32_t j = 0;
+    double se[8], sq[8], sn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, an[10];
+    if ((rc = d2h(&j, w->nno + i, 1, s)) || (rc = d2h(sq, T->v + 8 * (base + i), 8, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = d2h(se, O->v + 8 * (int64_t)j, 8, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const double t_s = gbp_host::pose_distance(sq, se) / V_NOM;
+    uint32_t f = 0;
+    const int32_t r = gbp_host::attempt_connect(t->host, se, sq, t_s, sn, an, cdir, adaptive,
+                                                GBP_CONNECT_MAX_DEPTH, &f);
+    const uint32_t fr = f | GBP_F_RESOLVED;
+    if ((rc = h2d(w->kres + i, &r, 1, s)) || (rc = h2d(w->kan + 10 * i, an, 10, s)) ||
+        (rc = h2d(w->kf + i, &fr, 1, s)))
+      return rc;
+    if (r != GBP_TRAPPED && (rc = h2d(w->ksn + 8 * i, sn, 8, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    ++*k;
+  }
+  return GBP_OK;
+}
+
+// the RRT* insertion's connect checks (their pair checks, rows of stage 6)
+static int resolve_star(gbp_terrain *t, gbp_plan_ws *w, const gbp_plan_status &st, int direction,
+                        int adaptive, hipStream_t s, int64_t *k) {
+  int rc;
+  const int64_t n = st.star_rows;
+  std::vector<uint32_t> rf(n);
+  const gbp_plan_ws::StarSet &S = w->ss[st.halt_half & 1];
+  if (n && (rc = d2h(rf.data(), S.srf, n, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  for (int64_t i = 0; i < n; i++) {
+    if (!(rf[i] & GBP_F_FRAGILE)) continue;
+    double sv[8], av[10], sn[8], tn = 0;
+    if ((rc = d2h(sv, S.srs + 8 * i, 8, s)) || (rc = d2h(av, S.sra + 10 * i, 10, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    uint32_t f = 0;
+    const bool v = gbp_host::pair_check(t->host, sv, av, direction, adaptive, sn, &tn, &f, nullptr);
+    const uint32_t fr = (f & ~GBP_F_FRAGILE) | (v ? GBP_F_VALID : 0u) | GBP_F_RESOLVED;
+    if ((rc = h2d(S.srf + i, &fr, 1, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    ++*k;
+  }
+  return GBP_OK;
+}
+
+// nothing to re-decide: the caller has grown the insertion sets
+// (gbp_plan_star_config); the half redoes its stage 6
+static int resolve_star_pairs(const gbp_plan_ws *w, const gbp_plan_status &st) {
+  return 2 * (int64_t)st.star_pairs > 2 * w->star_max_pairs ? GBP_E_SHAPE : GBP_OK;
 }
 
 int gbp_plan_resolve_host(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int direction,
@@ -3748,7 +3962,7 @@ int gbp_plan_resolve_host(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree 
                           gbp_stream stream) {
   if (!t || !w || !tree_ok(T)) return GBP_E_BAD_HANDLE;
   if (!resume_stage) return GBP_E_INVALID_ARG;
-  Guard g(t->device);
+  DeviceGuard g(t->device);
   hipStream_t s = (hipStream_t)stream;
   gbp_plan_status st;
   int rc = gbp_plan_status_read(w, &st, stream);
@@ -3756,137 +3970,31 @@ int gbp_plan_resolve_host(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree 
   *resume_stage = -1;
   int64_t k = 0;
   select_targets(w, st.halt_half >= 0 ? st.halt_half : 0);  // the halted half's target set
+  int resume = -1;  // the stage the half resumes at
   if (st.halt & GBP_PLAN_HALT_STAR_PAIRS) {
-    // nothing to re-decide: the caller has grown the insertion sets
-    // (gbp_plan_star_config); the half redoes its stage 6
-    if (2 * (int64_t)st.star_pairs > 2 * w->star_max_pairs) return GBP_E_SHAPE;
-    *resume_stage = 6;
+    rc = resolve_star_pairs(w, st);
+    resume = 6;
   } else if (st.halt & GBP_PLAN_HALT_TARGETS) {
-    // isValidState(s_rand, STANCE) of the half's draws (rrt_connect.cpp:254)
-    if (batch < 1 || batch > w->bmax) return GBP_E_INVALID_ARG;
-    std::vector<uint32_t> fl(batch);
-    if ((rc = d2h(fl.data(), w->cflag, batch, s))) return rc;
-    HIPCHK_P(hipStreamSynchronize(s));
-    for (int64_t i = 0; i < batch; i++) {
-      if (!(fl[i] & GBP_F_FRAGILE)) continue;
-      double q[8];
-      if ((rc = d2h(q, w->cand + 8 * i, 8, s))) return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      gbp_host::Acc acc;
-      const bool v = gbp_host::is_valid_state(t->host, q, GBP_STANCE, acc);
-      fl[i] = acc.flags | (v ? GBP_F_VALID : 0u) | GBP_F_RESOLVED;
-      if ((rc = h2d(w->cflag + i, &fl[i], 1, s))) return rc;
-      k++;
-    }
-    *resume_stage = 1;
+    rc = resolve_targets(t, w, batch, s, &k);
+    resume = 1;
   } else if (st.halt & GBP_PLAN_HALT_EXTEND) {
-    // newConfig + acceptance (rrt.cpp:20-101) of every extend with a FRAGILE
-    // executed candidate, on the device's own candidate actions
-    const int64_t n = st.n_targets;
-    std::vector<uint32_t> ef(n);
-    if ((rc = d2h(ef.data(), w->ef, n, s))) return rc;
-    HIPCHK_P(hipStreamSynchronize(s));
-    for (int64_t i = 0; i < n; i++) {
-      if (!(ef[i] & GBP_F_FRAGILE)) continue;
-      int32_t nn = 0;
-      double tg[8], sn0[8], act[10 * GBP_NUM_GEN_STATES];
-      if ((rc = d2h(&nn, w->nn + i, 1, s)) || (rc = d2h(tg, w->targets + 8 * i, 8, s)) ||
-          (rc = d2h(act, w->ca + 10 * GBP_NUM_GEN_STATES * i, 10 * GBP_NUM_GEN_STATES, s)))
-        return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      if ((rc = d2h(sn0, T->v + 8 * (int64_t)nn, 8, s))) return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      const double best0 = gbp_host::state_distance(sn0, tg);
-      double best = best0, s_test[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_test = 0, s_new[8];
-      uint32_t fl = 0;
-      int found = -1;
-      for (int j = 0; j < GBP_NUM_GEN_STATES; j++) {
-        uint32_t f = 0;
-        const bool v = gbp_host::pair_check(t->host, sn0, act + 10 * j, direction, adaptive, s_test,
-                                            &t_test, &f, nullptr);
-        fl |= f & (GBP_F_VALID | GBP_F_OOD | GBP_F_NAN | GBP_F_LIMIT);
-        if (v) {
-          found = j;
-          break;
-        }
-      }
-      int32_t r = GBP_TRAPPED;
-      if (found >= 0) {
-        const double cur = gbp_host::state_distance(s_test, tg);
-        if (cur < best) {
-          best = cur;
-          memcpy(s_new, s_test, sizeof s_new);
-          r = cur <= GOAL_BOUNDS ? GBP_REACHED : GBP_ADVANCED;
-          if ((rc = h2d(w->esn + 8 * i, s_new, 8, s)) ||
-              (rc = h2d(w->ean + 10 * i, act + 10 * found, 10, s)))
-            return rc;
-        }
-      }
-      const uint32_t fr = fl | GBP_F_RESOLVED;
-      if ((rc = h2d(w->eres + i, &r, 1, s)) || (rc = h2d(w->echo + i, &found, 1, s)) ||
-          (rc = h2d(w->ef + i, &fr, 1, s)))
-        return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      k++;
-    }
-    *resume_stage = 3;
+    rc = resolve_extend(t, w, T, st.n_targets, direction, adaptive, s, &k);
+    resume = 3;
   } else if (st.halt & GBP_PLAN_HALT_CONNECT) {
-    // RRTConnectClass::attemptConnect (rrt_connect.cpp:20-91) of every
-    // connection with a FRAGILE level, recursion replayed on the host
-    if (!tree_ok(O)) return GBP_E_BAD_HANDLE;
-    const int64_t n = st.n_added, base = st.added_base;
-    const int cdir = direction == GBP_FORWARD ? GBP_REVERSE : GBP_FORWARD;
-    std::vector<uint32_t> kf(n);
-    if ((rc = d2h(kf.data(), w->kf, n, s))) return rc;
-    HIPCHK_P(hipStreamSynchronize(s));
-    for (int64_t i = 0; i < n; i++) {
-      if (!(kf[i] & GBP_F_FRAGILE)) continue;
-      int32_t j = 0;
-      double se[8], sq[8], sn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, an[10];
-      if ((rc = d2h(&j, w->nno + i, 1, s)) || (rc = d2h(sq, T->v + 8 * (base + i), 8, s))) return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      if ((rc = d2h(se, O->v + 8 * (int64_t)j, 8, s))) return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      const double t_s = gbp_host::pose_distance(sq, se) / V_NOM;
-      uint32_t f = 0;
-      const int32_t r = gbp_host::attempt_connect(t->host, se, sq, t_s, sn, an, cdir, adaptive,
-                                                  GBP_CONNECT_MAX_DEPTH, &f);
-      const uint32_t fr = f | GBP_F_RESOLVED;
-      if ((rc = h2d(w->kres + i, &r, 1, s)) || (rc = h2d(w->kan + 10 * i, an, 10, s)) ||
-          (rc = h2d(w->kf + i, &fr, 1, s)))
-        return rc;
-      if (r != GBP_TRAPPED && (rc = h2d(w->ksn + 8 * i, sn, 8, s))) return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      k++;
-    }
-    *resume_stage = 5;
+    rc = resolve_connect(t, w, T, O, st, direction, adaptive, s, &k);
+    resume = 5;
   } else if (st.halt & GBP_PLAN_HALT_STAR) {
-    // the RRT* insertion's connect checks (their pair checks, rows of stage 6)
-    const int64_t n = st.star_rows;
-    std::vector<uint32_t> rf(n);
-    const gbp_plan_ws::StarSet &S = w->ss[st.halt_half & 1];
-    if (n && (rc = d2h(rf.data(), S.srf, n, s))) return rc;
-    HIPCHK_P(hipStreamSynchronize(s));
-    for (int64_t i = 0; i < n; i++) {
-      if (!(rf[i] & GBP_F_FRAGILE)) continue;
-      double sv[8], av[10], sn[8], tn = 0;
-      if ((rc = d2h(sv, S.srs + 8 * i, 8, s)) || (rc = d2h(av, S.sra + 10 * i, 10, s))) return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      uint32_t f = 0;
-      const bool v = gbp_host::pair_check(t->host, sv, av, direction, adaptive, sn, &tn, &f, nullptr);
-      const uint32_t fr = (f & ~GBP_F_FRAGILE) | (v ? GBP_F_VALID : 0u) | GBP_F_RESOLVED;
-      if ((rc = h2d(S.srf + i, &fr, 1, s))) return rc;
-      HIPCHK_P(hipStreamSynchronize(s));
-      k++;
-    }
-    *resume_stage = 7;
+    rc = resolve_star(t, w, st, direction, adaptive, s, &k);
+    resume = 7;
   }
-  if (*resume_stage >= 0) {
+  if (rc) return rc;
+  *resume_stage = resume;
+  if (resume >= 0) {
     st.halt = 0;
     if (!st.done) st.gate_seq = ~0ull;
     st.stat_fragile_resolved += k;
     if ((rc = h2d(w->st, &st, 1, s))) return rc;
-    HIPCHK_P(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(s));
   }
   if (n_resolved) *n_resolved = k;
   return GBP_OK;

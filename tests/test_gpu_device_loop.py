@@ -11,6 +11,8 @@ Reference: rrt_connect.cpp:230-314 (runRRTConnect), rrt.cpp:77-102 (extend),
 graph_class.cpp:28-42 (addVertex / addEdge), planner_class.cpp:185-200
 (getNearestNeighbor).
 """
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -248,4 +250,119 @@ def test_append_past_capacity_is_reported_not_faulted(gpu):
             break
     assert st["error"] & 2, (st["error"], st["done"], st["halt"])
     assert len(ta) <= 2 and len(tb) <= 2
+    torch.cuda.synchronize()
+
+
+def test_reserve_keeps_search_rows(gpu):
+    """gbp_tree_reserve carries the search's rows over: a tree created with 4
+    rows, grown by an append of 70 vertices (past the 64-row rounding of the
+    fp16 rows) and again by an append of 200, answers gbp_tree_nearest_dev
+    exactly as the fp64 scan over the same vertices does (the comparison of
+    test_tree_nearest_exact), through the matrix-core search (256 and 33
+    queries) and the direct one (1 query).  A reserve that dropped or
+    truncated the fp16 rows' copy, or lost their bounds, fails here."""
+    import global_body_planner_amd as gbp
+    T = gbp.Terrain.from_data(td.synth_rough(256), device=0)
+    verts = T.sample_states(271, seed=41, stream_id=1)[0].cpu().numpy()
+    q = T.sample_states(256, seed=42, stream_id=2)[0]
+    tree = gbp.DeviceTree(verts[0], device=0, capacity=4)
+    cap = ctypes.c_int64(0)
+    caps = []
+    for lo, hi in ((1, 71), (71, 271)):
+        tree.append(verts[lo:hi], np.zeros((hi - lo, 10)), np.zeros(hi - lo, np.int32))
+        L.check(L.load().gbp_tree_capacity(tree._h, ctypes.byref(cap)), "tree_capacity")
+        caps.append(cap.value)
+    assert len(tree) == 271 and 4 < caps[0] < caps[1], caps   # grown twice
+    ws = gbp.PlanWorkspace(T, 256)
+    vt = torch.from_numpy(verts).cuda()
+    for nqs in (256, 1, 33):
+        qt = q[:nqs].contiguous()
+        got = ws.nearest(tree, qt).cpu().numpy()
+        ref = gbp.nearest(qt, vt)[0].cpu().numpy()
+        bad = np.flatnonzero(got != ref)
+        assert bad.size == 0, (nqs, bad[:5], got[bad[:5]], ref[bad[:5]])
+
+
+@pytest.mark.parametrize("star,seed,groups", [(False, 3, 100), (True, 11, 80)])
+def test_reserve_between_groups_is_invisible(gpu, star, seed, groups):
+    """The same search driven twice in groups of 2 halves at batch 256
+    (RRT-Connect until it connects; RRT*-Connect, delta 3.0 and the planner's
+    caps, for a fixed number of groups): pair A in trees of 65536 rows from the
+    start, pair B in trees of 1 + 2 * 256 rows raised before every group by
+    gbp_tree_reserve to exactly len + 2 * 256, the host planner's sequence
+    (halts resolved by gbp_plan_resolve_host and resumed, in both).  After
+    every group the status records are equal, and at the end the trees are bit
+    for bit.  Pair A runs only what the oracle-parity tests pin, so it is the
+    reference.  Not vacuous: each of B's trees was moved to larger arrays at
+    least 3 times, and in the RRT* case rewires followed the first move, so g
+    depends on the successor lists the reserves copied."""
+    import global_body_planner_amd as gbp
+    batch = 256
+    data = td.synth_rough(256)
+    T = gbp.Terrain.from_data(data, device=0)
+    start, goal = _start_goal(oracle.OracleTerrain.from_data(data), 0.8, 0.8, 4.3, 4.3)
+    lib = L.load()
+
+    def capacity(tree):
+        c = ctypes.c_int64(0)
+        L.check(lib.gbp_tree_capacity(tree._h, ctypes.byref(c)), "tree_capacity")
+        return c.value
+
+    class Run:
+        def __init__(self, cap):
+            self.ws = gbp.PlanWorkspace(T, batch)
+            if star:
+                pairs = max(1 << 18, 8 * batch)   # the host planner's caps
+                L.check(self.ws._lib.gbp_plan_star_config(self.ws._h, 1, 3.0, pairs, 1 << 22),
+                        "star_config")
+            self.trees = [gbp.DeviceTree(s, device=0, capacity=cap) for s in (start, goal)]
+            self.ws.reset(0)
+
+        def group(self, half):
+            ws, (ta, tb) = self.ws, self.trees
+            ws.halves(T, ta, tb, half, 2, batch, seed=seed)
+            st = ws.status()
+            while st["halt"]:
+                assert not st["halt"] & L.PLAN_HALT_STAR_PAIRS   # the caps hold a half's pairs
+                h0 = st["halt_half"]
+                k = h0 & 1
+                resume, nres = ctypes.c_int(-1), ctypes.c_int64(0)
+                L.check(lib.gbp_plan_resolve_host(T._h, ws._h, self.trees[k]._h,
+                                                  self.trees[k ^ 1]._h,
+                                                  L.FORWARD if k == 0 else L.REVERSE, batch, 0,
+                                                  ctypes.byref(resume), ctypes.byref(nres), None),
+                        "plan_resolve")
+                assert resume.value >= 0
+                ws.halves(T, ta, tb, h0, half + 2 - h0, batch, seed=seed,
+                          first_stage=resume.value)
+                st = ws.status()
+            return st
+
+    A, B = Run(1 << 16), Run(1 + 2 * batch)
+    moved, rewires_at_first_move = [0, 0], None
+    sa = None
+    for gi in range(groups):
+        for k, tree in enumerate(B.trees):
+            want = len(tree) + 2 * batch
+            if want > capacity(tree):
+                L.check(lib.gbp_tree_reserve(tree._h, want, None), "tree_reserve")
+                assert capacity(tree) == want
+                moved[k] += 1
+                if rewires_at_first_move is None:
+                    rewires_at_first_move = sa["stat_rewires"] if sa else 0
+        sa, sb = A.group(2 * gi), B.group(2 * gi)
+        diff = {f: (sa[f], sb[f]) for f in sa if sa[f] != sb[f]}   # gate_seq included
+        assert not diff, (gi, diff)
+        assert not sa["error"], sa["error"]
+        if sa["done"]:
+            break
+    for ta, tb in zip(A.trees, B.trees):
+        for name, x, y in zip(("states", "actions", "parents", "g"), ta.read(), tb.read()):
+            assert x.shape == y.shape and x.tobytes() == y.tobytes(), name
+    print(f"star {star}: {gi + 1} groups, trees {len(A.trees[0])}+{len(A.trees[1])}, B's trees "
+          f"moved {moved} times, rewires {rewires_at_first_move} -> {sa['stat_rewires']}, "
+          f"{sa['stat_fragile_resolved']} re-decided")
+    assert min(moved) >= 3, moved
+    if star:
+        assert sa["stat_rewires"] > rewires_at_first_move, (rewires_at_first_move, sa["stat_rewires"])
     torch.cuda.synchronize()
