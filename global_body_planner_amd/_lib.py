@@ -56,6 +56,7 @@ EXPORTS = [
     "gbp_plan_halves_dev", "gbp_plan_star_config", "gbp_plan_stage_timing", "gbp_plan_stage_times",
     "gbp_plan_status_read", "gbp_plan_resolve_host", "gbp_extend_tree_dev",
     "gbp_extend_tree_finish_dev", "gbp_extend_tree_host", "gbp_tree_nearest_dev",
+    "gbp_shortcut_table_dev", "gbp_shortcut_paths_host",
 ]
 
 
@@ -165,6 +166,9 @@ def load(path=None):
         "gbp_extend_tree_finish_dev": (I, [P, P, P, I64, I, P, P, P]),
         "gbp_extend_tree_host": (I, [P, P, P, I64, P, I, I, U64, I64, P, P, P]),
         "gbp_tree_nearest_dev": (I, [P, P, I64, P, P, P]),
+        "gbp_shortcut_table_dev": (I, [P, I64, P, P, I, P, P, P]),
+        "gbp_shortcut_paths_host": (I, [P, I64, P, P, P, I, I, ctypes.c_double, ctypes.c_double,
+                                        P, P, P, P, P, P, P]),
         "gbp_nearest_batch_dev": (I, [I64, P, I64, P, P, P, P]),
         "gbp_nearest_batch_host": (I, [I64, P, I64, P, P, P]),
         "gbp_neighbors_batch_dev": (I, [I64, P, I64, P, ctypes.c_double, I, P, P, P]),

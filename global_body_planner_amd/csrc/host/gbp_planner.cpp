@@ -1124,6 +1124,27 @@ std::vector<Action> RRTConnectClass::getActionSequenceReverse(PlannerClass &T,
 void RRTConnectClass::postProcessPath(std::vector<State> &state_sequence,
                                       std::vector<Action> &action_sequence,
                                       FastTerrainMap &terrain) {  // rrt_connect.cpp:139-227
+  if (post_process_device_ && state_sequence.size() >= 2 &&
+      action_sequence.size() + 1 == state_sequence.size()) {
+    // the same walk over one table of all the path's connect decisions
+    const int64_t n = (int64_t)state_sequence.size(), off[2] = {0, n};
+    int64_t out_off[2] = {0, 0};
+    std::vector<State> new_states(n);
+    std::vector<Action> new_actions(n - 1);
+    chk(gbp_shortcut_paths_host(terrain.handle(), 1, off, state_sequence[0].data(),
+                                action_sequence[0].data(),
+                                state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0,
+                                cost_add_yaw_flag_ ? 1 : 0, cost_add_yaw_length_weight_,
+                                cost_add_yaw_yaw_weight_, out_off, new_states[0].data(),
+                                new_actions[0].data(), &path_length_, &path_yaw_, &path_cost_,
+                                nullptr),
+        "postProcessPath");
+    new_states.resize(out_off[1]);
+    new_actions.resize(out_off[1] - 1);
+    state_sequence = new_states;
+    action_sequence = new_actions;
+    return;
+  }
   State s = state_sequence.front();
   const State s_goal = state_sequence.back();
   State dummy{};
@@ -2391,6 +2412,7 @@ extern "C" int gbp_plan_rrt_connect(const gbp_plan_params *p, gbp_plan_result *r
                                          p->sampling.state_speed_direction != 0);
     planner.set_action_direction_sampling(p->sampling.action_flag != 0, p->sampling.action_p);
     planner.set_state_action_pair_check_adaptive_step_size_flag_(p->adaptive != 0);
+    planner.set_post_process_device(p->post_process == 2);
     State s0, s1;
     std::copy(p->start, p->start + 8, s0.begin());
     std::copy(p->goal, p->goal + 8, s1.begin());

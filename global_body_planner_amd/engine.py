@@ -190,6 +190,24 @@ class Terrain:
                                                 valid_ptr, snew_ptr, tnew_ptr, flags_ptr,
                                                 counts_ptr, stream_ptr)
 
+    def shortcut_table(self, paths, adaptive=False):
+        """postProcessPath's connect decisions (rrt_connect.cpp:139-227,
+        gbp_shortcut_table_dev) for a list of [n_p][8] paths: (reached uint8,
+        flags int32), one entry per pair i < j of each path, a path's pairs
+        packed row-major over the upper triangle, the paths' consecutive.
+        FRAGILE items are left flagged (planner.shortcut_paths re-decides them)."""
+        ps = [self._dev(p, torch.float64, (8,)) for p in paths]
+        off = np.zeros(len(ps) + 1, np.int64)
+        off[1:] = np.cumsum([p.shape[0] for p in ps])
+        items = int(sum(p.shape[0] * (p.shape[0] - 1) // 2 for p in ps))
+        st = torch.cat(ps) if ps else self._empty((0, 8), torch.float64)
+        reached = self._empty(items, torch.uint8)
+        flags = self._empty(items, torch.int32)
+        check(self._lib.gbp_shortcut_table_dev(self._h, len(ps), _np_ptr(off), _ptr(st),
+                                               int(bool(adaptive)), _ptr(reached), _ptr(flags),
+                                               _stream(self.device)), "shortcut_table")
+        return reached, flags
+
     # ---- K3 -------------------------------------------------------------------
     def sample_states(self, n, seed, stream_id, index_base=0, require_phase=-1, max_tries=1):
         st = self._empty((n, 8), torch.float64)

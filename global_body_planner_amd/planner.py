@@ -250,6 +250,53 @@ def plan_rrt_connect_anytime(data, start, goal, max_time_opt=1.0, device_loop=Fa
                             max_time_opt=max_time_opt, **kw)
 
 
+def shortcut_paths(terrain_or_data, paths, actions, adaptive=False, cost_add_yaw=False,
+                   length_weight=1.0, yaw_weight=1.0, device=0):
+    """RRTConnectClass::postProcessPath (rrt_connect.cpp:139-227) for several
+    found paths in one call (gbp_shortcut_paths_host): every connect decision
+    of every path in one launch, then each path's walk on the host.
+
+    terrain_or_data: an engine.Terrain, or a terrain_data.TerrainData (a
+    Terrain is made for the call on `device`); paths: a list of [n_p][8] state
+    arrays (n_p >= 2); actions: their [n_p - 1][10] edge actions.
+    Returns a dict: `states` / `actions` (lists, one array per path: what the
+    walk keeps), `path_length`, `path_yaw`, `path_cost` (arrays [n_paths], the
+    reference's path_length_ / path_yaw_ / path_cost_) and `n_resolved` (pairs
+    re-decided on the host)."""
+    from . import engine
+    own = not isinstance(terrain_or_data, engine.Terrain)
+    T = engine.Terrain.from_data(terrain_or_data, device=device) if own else terrain_or_data
+    try:
+        ps = [np.ascontiguousarray(p, np.float64).reshape(-1, 8) for p in paths]
+        acs = [np.ascontiguousarray(a, np.float64).reshape(-1, 10) for a in actions]
+        if len(ps) != len(acs) or any(a.shape[0] != p.shape[0] - 1 for p, a in zip(ps, acs)):
+            raise ValueError("each path of n states takes n - 1 actions")
+        n_paths = len(ps)
+        off = np.zeros(n_paths + 1, np.int64)
+        off[1:] = np.cumsum([p.shape[0] for p in ps])
+        total = int(off[-1])
+        st = np.concatenate(ps) if ps else np.zeros((0, 8))
+        ac = np.concatenate(acs) if acs else np.zeros((0, 10))
+        out_off = np.zeros(n_paths + 1, np.int64)
+        os_, oa = np.zeros((max(total, 1), 8)), np.zeros((max(total - n_paths, 1), 10))
+        ln, yw, co = np.zeros(max(n_paths, 1)), np.zeros(max(n_paths, 1)), np.zeros(max(n_paths, 1))
+        nres = ctypes.c_int64(0)
+        rc = T._lib.gbp_shortcut_paths_host(
+            T._h, n_paths, off.ctypes.data, st.ctypes.data, ac.ctypes.data, int(bool(adaptive)),
+            int(bool(cost_add_yaw)), float(length_weight), float(yaw_weight), out_off.ctypes.data,
+            os_.ctypes.data, oa.ctypes.data, ln.ctypes.data, yw.ctypes.data, co.ctypes.data,
+            ctypes.byref(nres))
+        if rc != 0:
+            raise _lib.GbpError(rc, "gbp_shortcut_paths_host")
+    finally:
+        if own:
+            T.close()
+    return {"states": [os_[out_off[p]:out_off[p + 1]].copy() for p in range(n_paths)],
+            "actions": [oa[out_off[p] - p:out_off[p + 1] - p - 1].copy() for p in range(n_paths)],
+            "path_length": ln[:n_paths].copy(), "path_yaw": yw[:n_paths].copy(),
+            "path_cost": co[:n_paths].copy(), "n_resolved": nres.value}
+
+
 def attempt_connect(terrain, s_existing, s, direction, t_s=None, adaptive=False, s_new=None,
                     a_new=None):
     """RRTConnectClass::attemptConnect (rrt_connect.cpp:20-91) for n pairs on an

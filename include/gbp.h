@@ -619,6 +619,48 @@ int gbp_extend_tree_host(gbp_terrain *t, gbp_plan_ws *ws, gbp_tree *T, int64_t n
                          int64_t extend_base, int32_t *result, int32_t *new_vertex,
                          int64_t *n_resolved);
 
+/* ---- path shortcutting (RRTConnectClass::postProcessPath,
+ *      rrt_connect.cpp:139-227) ------------------------------------------------
+ * The walk keeps a state, then connects it to the farthest later state that
+ * attemptConnect(s, s_next, FORWARD) REACHES.  That decision depends on the two
+ * states and the terrain alone (the recursion's depth 0: t_s = poseDistance /
+ * V_NOM > KINEMATICS_RES, isValidAction of the connect action, one valid pair
+ * check), so the decisions of all pairs of all paths of a call are made in one
+ * launch and the walk is replayed over the table.
+ * n_paths paths: path p is the states [path_off[p], path_off[p + 1]) of
+ * states[total][8], path_off[0] = 0, at least two states each (path_off is a
+ * HOST array of n_paths + 1).  Pair (i, j), i < j, of path p with n states is
+ * item pair_off[p] + i (2n - i - 1) / 2 + (j - i - 1), pair_off[p] = the pairs
+ * of the paths before it (row-major upper triangle; n (n - 1) / 2 per path).
+ *
+ * gbp_shortcut_table_dev (rrt_connect.cpp:139-227, the walk's :166 decisions):
+ * states on the device; reached[item] = 1 where the connect is REACHED, else 0;
+ * flags[item] = the pair check's GBP_F_OOD / NAN / FRAGILE / LIMIT bits (0
+ * where none ran).  Enqueue-only on `stream`; a FRAGILE item is left to the
+ * caller to re-decide. */
+int gbp_shortcut_table_dev(gbp_terrain *t, int64_t n_paths, const int64_t *path_off,
+                           const double *states, int adaptive, uint8_t *reached, uint32_t *flags,
+                           gbp_stream stream);
+/* postProcessPath (rrt_connect.cpp:139-227) for n_paths paths, host pointers,
+ * synchronous: one table launch, one read-back, the FRAGILE items re-decided
+ * with glibc (*n_resolved, may be NULL), then each path's walk.
+ * actions[total - n_paths][10]: path p's n_p - 1 edge actions (action k leads
+ * into state k + 1), the paths' consecutive.  Outputs, packed the same way:
+ * path p keeps the states [out_off[p], out_off[p + 1]) of out_states (capacity
+ * total: the walk never lengthens a path) and one action fewer in out_actions
+ * (capacity total - n_paths); out_off[n_paths + 1].  A kept connect action is
+ * the one attemptConnect forms (:53-63); a state the walk cannot connect to
+ * any later one keeps its successor and original action.  path_length[p],
+ * path_yaw[p], path_cost[p] as the reference leaves path_length_ / path_yaw_ /
+ * path_cost_ (the cost is the length, or with cost_add_yaw_flag the sum of
+ * length * length_weight + yaw * yaw_weight per edge). */
+int gbp_shortcut_paths_host(gbp_terrain *t, int64_t n_paths, const int64_t *path_off,
+                            const double *states, const double *actions, int adaptive,
+                            int cost_add_yaw_flag, double length_weight, double yaw_weight,
+                            int64_t *out_off, double *out_states, double *out_actions,
+                            double *path_length, double *path_yaw, double *path_cost,
+                            int64_t *n_resolved);
+
 #ifdef __cplusplus
 }
 #endif

@@ -496,6 +496,12 @@ class RRTConnectClass : public RRTClass {
   // runRRTConnect, one engine call per extend / connect.
   void set_engine_batch(int batch) { engine_batch_ = batch; }
   int engine_batch() const { return engine_batch_; }
+  // postProcessPath's connect decisions as one table launch
+  // (gbp_shortcut_paths_host) instead of one attemptConnect per popped
+  // candidate: the same kept states, actions and path_length_ / path_yaw_ /
+  // path_cost_.  Off by default.
+  void set_post_process_device(bool on) { post_process_device_ = on; }
+  bool post_process_device() const { return post_process_device_; }
 
   // attemptConnect for many independent pairs (lock-step rounds, one engine
   // launch per recursion depth); s_new / a_new are in/out per pair
@@ -513,6 +519,7 @@ class RRTConnectClass : public RRTClass {
   double horizon_expansion_factor = 1.2;
   const int max_time_solve = 4000;
   int engine_batch_ = 1024;
+  bool post_process_device_ = false;
 
   // lock-step attemptConnect for many (s_existing, s, t_s) triples; with
   // max_depth = 0 only REACHED is decided (callers that test == REACHED)
@@ -644,7 +651,8 @@ typedef struct {
   int batch;            // targets per half-iteration (1 = sequential runRRTConnect)
   double max_time;      // seconds
   uint64_t seed;
-  int post_process;     // run postProcessPath on the found path
+  int post_process;     // nonzero: run postProcessPath on the found path; 2: with its
+                        // connect decisions as one table launch (set_post_process_device)
   int algorithm;        // 0 rrt-connect (first solution), 1 rrt-star-connect (anytime
                         // until max_time), 2 rrt-connect with the reference's anytime
                         // restarts (best post-processed path after max_time_opt),
