@@ -3,8 +3,10 @@
 // (propagation closed forms, isValidAction, distances, connect actions) is
 // the reference's.  Every terrain query / state check / NN scan / candidate
 // sampling goes through include/gbp.h (the HIP engine): there is no CPU
-// evaluation of the validity path here.
+// evaluation of the validity path here.  The engine-free arithmetic of
+// planning_utils is gbp_planning_math.cpp, the path join gbp_tree_path.cpp.
 #include "gbp_planner.h"
+#include "gbp_tree_path.h"
 #include "../gbp_um_order.h"
 
 #include <algorithm>
@@ -25,8 +27,14 @@ static void chk(int rc, const char *what) {
   if (rc != GBP_OK) throw EngineError(rc, what);
 }
 
-static inline double std_min(double a, double b) { return (b < a) ? b : a; }
-static inline double std_max(double a, double b) { return (a < b) ? b : a; }
+// seconds since its construction, on the clock every search times itself with
+struct Stopwatch {
+  const std::chrono::high_resolution_clock::time_point t0 = std::chrono::high_resolution_clock::now();
+  std::chrono::duration<double> elapsed() const {
+    return std::chrono::high_resolution_clock::now() - t0;
+  }
+  double seconds() const { return elapsed().count(); }
+};
 
 // ============================================================================
 // terrain ingest (terrain_map_publisher.cpp:290-370, fast_terrain_map.cpp:31-91)
@@ -244,132 +252,6 @@ void setRandomSeed(uint64_t seed) {
   g_action_draws = 0;
 }
 
-State interp(State q1, State q2, double x) {  // planning_utils.cpp:97-103
-  State q;
-  for (int d = 0; d < 8; d++) q[d] = (q2[d] - q1[d]) * x + q1[d];
-  return q;
-}
-
-double poseDistance(const State &q1, const State &q2) {  // :106-115
-  double sum = 0;
-  for (int i = 0; i < POSEDIM; i++) sum = sum + (q2[i] - q1[i]) * (q2[i] - q1[i]);
-  return std::sqrt(sum);
-}
-
-double stateDistance(const State &q1, const State &q2) {  // :116-127
-  double sum = 0;
-  for (int i = 0; i < 8; i++) sum = sum + 1.0 * (q2[i] - q1[i]) * (q2[i] - q1[i]);
-  return std::sqrt(sum);
-}
-
-double stateYawDistance(const State &q1, const State &q2) {  // planning_utils.h:133-145
-  const double yaw1 = std::atan2(q1[4], q1[3]);
-  const double yaw2 = std::atan2(q2[4], q2[3]);
-  const double yaw_min = std_min(yaw1, yaw2), yaw_max = std_max(yaw1, yaw2);
-  return std_min(yaw_max - yaw_min, yaw_min + 2 * MY_PI - yaw_max);
-}
-
-double stateDistance(const State &q1, const State &q2, bool f, double lw, double yw) {
-  if (f) return poseDistance(q1, q2) * lw + stateYawDistance(q1, q2) * yw;
-  return stateDistance(q1, q2);
-}
-
-bool isWithinBounds(State s1, State s2) { return stateDistance(s1, s2) <= GOAL_BOUNDS; }
-
-State applyStance(State s, Action a, double t) {  // :237-274
-  const double a_x_td = a[0], a_y_td = a[1], a_z_td = a[2];
-  const double a_x_to = a[3], a_y_to = a[4], a_z_to = a[5];
-  const double t_s = a[6], a_p_td = a[8], a_p_to = a[9];
-  State o;
-  o[0] = s[0] + s[3] * t + 0.5 * a_x_td * t * t + (a_x_to - a_x_td) * (t * t * t) / (6.0 * t_s);
-  o[1] = s[1] + s[4] * t + 0.5 * a_y_td * t * t + (a_y_to - a_y_td) * (t * t * t) / (6.0 * t_s);
-  o[2] = s[2] + s[5] * t + 0.5 * a_z_td * t * t + (a_z_to - a_z_td) * (t * t * t) / (6.0 * t_s);
-  o[3] = s[3] + a_x_td * t + (a_x_to - a_x_td) * t * t / (2.0 * t_s);
-  o[4] = s[4] + a_y_td * t + (a_y_to - a_y_td) * t * t / (2.0 * t_s);
-  o[5] = s[5] + a_z_td * t + (a_z_to - a_z_td) * t * t / (2.0 * t_s);
-  o[6] = s[6] + s[7] * t + 0.5 * a_p_td * t * t + (a_p_to - a_p_td) * (t * t * t) / (6.0 * t_s);
-  o[7] = s[7] + a_p_td * t + (a_p_to - a_p_td) * t * t / (2.0 * t_s);
-  return o;
-}
-
-State applyStance(State s, Action a) { return applyStance(s, a, a[6]); }
-
-State applyFlight(State s, double t_f) {  // :282-306
-  const double g = 9.81;
-  State o;
-  o[0] = s[0] + s[3] * t_f;
-  o[1] = s[1] + s[4] * t_f;
-  o[2] = s[2] + s[5] * t_f - 0.5 * g * t_f * t_f;
-  o[3] = s[3];
-  o[4] = s[4];
-  o[5] = s[5] - g * t_f;
-  o[6] = s[6] + s[7] * t_f;
-  o[7] = s[7];
-  return o;
-}
-
-State applyAction(State s, Action a) { return applyFlight(applyStance(s, a), a[7]); }
-
-State applyStanceReverse(State s, Action a, double t) {  // :324-367
-  const double a_x_td = a[0], a_y_td = a[1], a_z_td = a[2];
-  const double a_x_to = a[3], a_y_to = a[4], a_z_to = a[5];
-  const double t_s = a[6], a_p_td = a[8], a_p_to = a[9];
-  const double cx = s[3] - a_x_td * t_s - 0.5 * (a_x_to - a_x_td) * t_s;
-  const double cy = s[4] - a_y_td * t_s - 0.5 * (a_y_to - a_y_td) * t_s;
-  const double cz = s[5] - a_z_td * t_s - 0.5 * (a_z_to - a_z_td) * t_s;
-  const double cp = s[7] - a_p_td * t_s - 0.5 * (a_p_to - a_p_td) * t_s;
-  State o;
-  o[0] = s[0] - cx * (t_s - t) - 0.5 * a_x_td * (t_s * t_s - t * t) -
-         (a_x_to - a_x_td) * (t_s * t_s * t_s - t * t * t) / (6.0 * t_s);
-  o[1] = s[1] - cy * (t_s - t) - 0.5 * a_y_td * (t_s * t_s - t * t) -
-         (a_y_to - a_y_td) * (t_s * t_s * t_s - t * t * t) / (6.0 * t_s);
-  o[2] = s[2] - cz * (t_s - t) - 0.5 * a_z_td * (t_s * t_s - t * t) -
-         (a_z_to - a_z_td) * (t_s * t_s * t_s - t * t * t) / (6.0 * t_s);
-  o[3] = s[3] - a_x_td * (t_s - t) - (a_x_to - a_x_td) * (t_s * t_s - t * t) / (2.0 * t_s);
-  o[4] = s[4] - a_y_td * (t_s - t) - (a_y_to - a_y_td) * (t_s * t_s - t * t) / (2.0 * t_s);
-  o[5] = s[5] - a_z_td * (t_s - t) - (a_z_to - a_z_td) * (t_s * t_s - t * t) / (2.0 * t_s);
-  o[7] = s[7] - a_p_td * (t_s - t) - (a_p_to - a_p_td) * (t_s * t_s - t * t) / (2.0 * t_s);
-  o[6] = s[6] - cp * (t_s - t) - 0.5 * a_p_td * (t_s * t_s - t * t) -
-         (a_p_to - a_p_td) * (t_s * t_s * t_s - t * t * t) / (6.0 * t_s);
-  return o;
-}
-
-State applyStanceReverse(State s, Action a) { return applyStanceReverse(s, a, 0); }
-
-std::array<double, 3> rotate_grf(std::array<double, 3> n, std::array<double, 3> f) {  // :198-231
-  const double v0 = n[1] * 1.0 - n[2] * 0.0, v1 = n[2] * 0.0 - n[0] * 1.0,
-               v2 = n[0] * 0.0 - n[1] * 0.0;
-  const double s = std::sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-  const double c = n[0] * 0.0 + n[1] * 0.0 + n[2] * 1.0;
-  if (s < 0.000001) return f;
-  const double K[3][3] = {{0, -v2, v1}, {v2, 0, -v0}, {-v1, v0, 0}};
-  std::array<double, 3> out;
-  for (int i = 0; i < 3; i++) {
-    double acc = 0;
-    for (int j = 0; j < 3; j++) {
-      const double kk = K[i][0] * K[0][j] + K[i][1] * K[1][j] + K[i][2] * K[2][j];
-      const double r = (i == j ? 1.0 : 0.0) + K[i][j] + kk * (1 - c) / (s * s);
-      acc = j == 0 ? r * f[0] : acc + r * f[j];
-    }
-    out[i] = acc;
-  }
-  return out;
-}
-
-bool isValidAction(Action a) {  // :519-556
-  if ((a[6] <= 0) || (a[7] < 0)) return false;
-  const double m = M_CONST, g = G_CONST, mu = MU;
-  const double f_x_td = m * a[0], f_y_td = m * a[1], f_z_td = m * (a[2] + g);
-  const double f_x_to = m * a[3], f_y_to = m * a[4], f_z_to = m * (a[5] + g);
-  if ((std::sqrt(f_x_td * f_x_td + f_y_td * f_y_td + f_z_td * f_z_td) >= F_MAX) ||
-      (std::sqrt(f_x_to * f_x_to + f_y_to * f_y_to + f_z_to * f_z_to) >= F_MAX) || (f_z_td < 0) ||
-      (f_z_to < 0) || (a[8] >= F_MAX) || (a[9] >= F_MAX))
-    return false;
-  if ((std::sqrt(f_x_td * f_x_td + f_y_td * f_y_td) >= mu * f_z_td) ||
-      (std::sqrt(f_x_to * f_x_to + f_y_to * f_y_to) >= mu * f_z_to))
-    return false;
-  return true;
-}
 
 bool isValidState(State s, FastTerrainMap &terrain, int phase) {
   uint8_t v;
@@ -529,47 +411,35 @@ using namespace planning_utils;
 // ============================================================================
 PlannerClass::PlannerClass(int device) : device_(device) {}
 
-PlannerClass::~PlannerClass() {
-  if (d_vertices_) gbp_device_free(d_vertices_);
-  if (d_scratch_) gbp_device_free(d_scratch_);
-  if (d_nbr_) gbp_device_free(d_nbr_);
-  if (d_yaw_) gbp_device_free(d_yaw_);
+DeviceBuffer::~DeviceBuffer() {
+  if (p_) gbp_device_free(p_);
 }
 
-PlannerClass::PlannerClass(const PlannerClass &o)
-    : device_(o.device_), vertices_(o.vertices_), actions_(o.actions_), parent_(o.parent_),
-      successors_(o.successors_), g_(o.g_), y_(o.y_), cost_add_yaw_flag_(o.cost_add_yaw_flag_),
-      cost_add_yaw_length_weight_(o.cost_add_yaw_length_weight_),
-      cost_add_yaw_yaw_weight_(o.cost_add_yaw_yaw_weight_), seed_(o.seed_),
-      stream_id_(o.stream_id_), draws_(o.draws_) {}
-
-PlannerClass &PlannerClass::operator=(const PlannerClass &o) {
-  if (this == &o) return *this;
-  if (d_vertices_) gbp_device_free(d_vertices_);
-  if (d_scratch_) gbp_device_free(d_scratch_);
-  if (d_nbr_) gbp_device_free(d_nbr_);
-  if (d_yaw_) gbp_device_free(d_yaw_);
-  d_vertices_ = nullptr;
-  d_scratch_ = nullptr;
-  d_nbr_ = nullptr;
-  d_yaw_ = nullptr;
-  d_capacity_ = d_count_ = d_scratch_cap_ = 0;
-  d_yaw_cap_ = d_yaw_count_ = 0;
-  d_nbr_bytes_ = 0;
-  device_ = o.device_;
-  vertices_ = o.vertices_;
-  actions_ = o.actions_;
-  parent_ = o.parent_;
-  successors_ = o.successors_;
-  g_ = o.g_;
-  y_ = o.y_;
-  cost_add_yaw_flag_ = o.cost_add_yaw_flag_;
-  cost_add_yaw_length_weight_ = o.cost_add_yaw_length_weight_;
-  cost_add_yaw_yaw_weight_ = o.cost_add_yaw_yaw_weight_;
-  seed_ = o.seed_;
-  stream_id_ = o.stream_id_;
-  draws_ = o.draws_;
+DeviceBuffer &DeviceBuffer::operator=(DeviceBuffer &&o) noexcept {
+  if (this != &o) {
+    if (p_) gbp_device_free(p_);
+    p_ = std::exchange(o.p_, nullptr);
+    cap_ = std::exchange(o.cap_, 0);
+    valid = std::exchange(o.valid, 0);
+  }
   return *this;
+}
+
+void DeviceBuffer::reserve(int device, int64_t n, size_t elem_bytes, int64_t min_elems,
+                           const char *what) {
+  if (n <= cap_) return;
+  int64_t cap = std::max(min_elems, cap_);
+  while (cap < n) cap *= 2;
+  void *p = nullptr;
+  chk(gbp_device_alloc(device, (size_t)cap * elem_bytes, &p), what);
+  if (p_) gbp_device_free(p_);
+  p_ = p;
+  cap_ = cap;
+  valid = 0;
+}
+
+TreeView PlannerClass::treeView() const {
+  return {vertices_.data(), actions_.data(), parent_.data(), g_.data()};
 }
 
 void PlannerClass::init(State s, bool f, double lw, double yw) {  // graph_class.cpp:141-152
@@ -579,8 +449,8 @@ void PlannerClass::init(State s, bool f, double lw, double yw) {  // graph_class
   successors_.clear();
   g_.clear();
   y_.clear();
-  d_count_ = 0;
-  d_yaw_count_ = 0;
+  d_.vertices.valid = 0;
+  d_.yaw.valid = 0;
   addVertex(0, s);
   g_[0] = 0;
   y_[0] = 0;
@@ -599,8 +469,8 @@ void PlannerClass::addVertex(int idx, State s) {
     y_.resize(idx + 1, 0);
   }
   vertices_[idx] = s;
-  if (idx < d_count_) d_count_ = idx;  // re-upload from here
-  if (idx < d_yaw_count_) d_yaw_count_ = idx;
+  if (idx < d_.vertices.valid) d_.vertices.valid = idx;  // re-upload from here
+  if (idx < d_.yaw.valid) d_.yaw.valid = idx;
 }
 
 void PlannerClass::addEdge(int idx1, int idx2) {  // graph_class.cpp:36-42
@@ -632,44 +502,28 @@ void PlannerClass::updateGYValue(int idx, double g_val, double y_val) {  // :131
 
 void PlannerClass::sync_device() {
   const int64_t V = (int64_t)vertices_.size();
-  if (V > d_capacity_) {
-    int64_t cap = std::max<int64_t>(1024, d_capacity_);
-    while (cap < V) cap *= 2;
-    void *p = nullptr;
-    chk(gbp_device_alloc(device_, (size_t)cap * sizeof(State), &p), "tree alloc");
-    if (d_vertices_) gbp_device_free(d_vertices_);
-    d_vertices_ = (double *)p;
-    d_capacity_ = cap;
-    d_count_ = 0;
-  }
-  if (d_count_ < V) {
-    chk(gbp_memcpy_h2d(d_vertices_ + 8 * d_count_, vertices_[d_count_].data(),
-                       (size_t)(V - d_count_) * sizeof(State), nullptr),
+  DeviceBuffer &b = d_.vertices;
+  b.reserve(device_, V, sizeof(State), 1024, "tree alloc");
+  if (b.valid < V) {
+    chk(gbp_memcpy_h2d(b.data<double>() + 8 * b.valid, vertices_[b.valid].data(),
+                       (size_t)(V - b.valid) * sizeof(State), nullptr),
         "tree upload");
     chk(gbp_stream_synchronize(nullptr), "tree upload");  // pageable source
-    d_count_ = V;
+    b.valid = V;
   }
 }
 
 void PlannerClass::sync_yaw() {
   const int64_t V = (int64_t)vertices_.size();
-  if (V > d_yaw_cap_) {
-    int64_t cap = std::max<int64_t>(1024, d_yaw_cap_);
-    while (cap < V) cap *= 2;
-    void *p = nullptr;
-    chk(gbp_device_alloc(device_, (size_t)cap * sizeof(double), &p), "yaw alloc");
-    if (d_yaw_) gbp_device_free(d_yaw_);
-    d_yaw_ = (double *)p;
-    d_yaw_cap_ = cap;
-    d_yaw_count_ = 0;
-  }
-  if (d_yaw_count_ < V) {
-    std::vector<double> y((size_t)(V - d_yaw_count_));
-    for (int64_t i = d_yaw_count_; i < V; i++) y[i - d_yaw_count_] = gbp_host_yaw(vertices_[i].data());
-    chk(gbp_memcpy_h2d(d_yaw_ + d_yaw_count_, y.data(), y.size() * sizeof(double), nullptr),
+  DeviceBuffer &b = d_.yaw;
+  b.reserve(device_, V, sizeof(double), 1024, "yaw alloc");
+  if (b.valid < V) {
+    std::vector<double> y((size_t)(V - b.valid));
+    for (int64_t i = b.valid; i < V; i++) y[i - b.valid] = gbp_host_yaw(vertices_[i].data());
+    chk(gbp_memcpy_h2d(b.data<double>() + b.valid, y.data(), y.size() * sizeof(double), nullptr),
         "yaw upload");
     chk(gbp_stream_synchronize(nullptr), "yaw upload");  // pageable source
-    d_yaw_count_ = V;
+    b.valid = V;
   }
 }
 
@@ -721,15 +575,7 @@ std::vector<State> PlannerClass::randomStateBatch(FastTerrainMap &terrain, int n
 }
 
 void PlannerClass::ensure_scratch(int64_t nq) {
-  if (nq <= d_scratch_cap_) return;
-  int64_t cap = std::max<int64_t>(256, d_scratch_cap_);
-  while (cap < nq) cap *= 2;
-  void *p = nullptr;
-  chk(gbp_device_alloc(device_, (size_t)cap * (sizeof(State) + sizeof(int32_t)), &p),
-      "nn scratch alloc");
-  if (d_scratch_) gbp_device_free(d_scratch_);
-  d_scratch_ = p;
-  d_scratch_cap_ = cap;
+  d_.scratch.reserve(device_, nq, sizeof(State) + sizeof(int32_t), 256, "nn scratch alloc");
 }
 
 std::vector<int> PlannerClass::getNearestNeighborBatch(const std::vector<State> &q) {
@@ -738,11 +584,12 @@ std::vector<int> PlannerClass::getNearestNeighborBatch(const std::vector<State> 
   sync_device();
   const int64_t nq = (int64_t)q.size();
   ensure_scratch(nq);
-  double *dq = (double *)d_scratch_;
-  int32_t *di = (int32_t *)(dq + 8 * d_scratch_cap_);
+  double *dq = d_.scratch.data<double>();
+  int32_t *di = (int32_t *)(dq + 8 * d_.scratch.capacity());
   std::vector<int32_t> out(nq);
   chk(gbp_memcpy_h2d(dq, q[0].data(), (size_t)nq * sizeof(State), nullptr), "nn upload");
-  chk(gbp_nearest_batch_dev(nq, dq, (int64_t)vertices_.size(), d_vertices_, di, nullptr, nullptr),
+  chk(gbp_nearest_batch_dev(nq, dq, (int64_t)vertices_.size(), d_.vertices.data<double>(), di,
+                            nullptr, nullptr),
       "getNearestNeighbor");
   chk(gbp_memcpy_d2h(out.data(), di, (size_t)nq * sizeof(int32_t), nullptr), "nn download");
   chk(gbp_stream_synchronize(nullptr), "nn sync");
@@ -766,20 +613,14 @@ std::vector<std::vector<int>> PlannerClass::neighborhoodDistBatch(const std::vec
   int max_out = 256;
   for (int pass = 0; pass < 2; pass++) {
     const size_t bytes = (size_t)nq * (sizeof(State) + sizeof(int32_t) * (max_out + 1)) + 256;
-    if (bytes > d_nbr_bytes_) {
-      if (d_nbr_) gbp_device_free(d_nbr_);
-      d_nbr_ = nullptr;
-      d_nbr_bytes_ = 0;
-      chk(gbp_device_alloc(device_, bytes, &d_nbr_), "neighbourhood scratch");
-      d_nbr_bytes_ = bytes;
-    }
-    double *dq = (double *)d_nbr_;
+    d_.nbr.reserve(device_, (int64_t)bytes, 1, (int64_t)bytes, "neighbourhood scratch");  // exactly
+    double *dq = d_.nbr.data<double>();
     int32_t *dcnt = (int32_t *)(dq + 8 * nq);
     int32_t *dout = dcnt + nq;
     std::vector<int32_t> cnt(nq), lst((size_t)nq * max_out);
     chk(gbp_memcpy_h2d(dq, q[0].data(), (size_t)nq * sizeof(State), nullptr), "nbr upload");
-    chk(gbp_neighbors_batch_dev(nq, dq, (int64_t)vertices_.size(), d_vertices_, dist, max_out, dout,
-                                dcnt, nullptr),
+    chk(gbp_neighbors_batch_dev(nq, dq, (int64_t)vertices_.size(), d_.vertices.data<double>(), dist,
+                                max_out, dout, dcnt, nullptr),
         "neighborhoodDist");
     chk(gbp_memcpy_d2h(cnt.data(), dcnt, (size_t)nq * sizeof(int32_t), nullptr), "nbr count");
     chk(gbp_memcpy_d2h(lst.data(), dout, lst.size() * sizeof(int32_t), nullptr), "nbr list");
@@ -818,7 +659,7 @@ std::vector<int> PlannerClass::neighborhoodN(State q, int N) {  // :151-171
     // weighted distance (:157-158) on the vertices' glibc yaws
     sync_device();
     ensure_scratch(256);  // one query row (+ its yaw) + N indices
-    double *dq = (double *)d_scratch_;
+    double *dq = d_.scratch.data<double>(), *dv = d_.vertices.data<double>();
     int32_t *dout = (int32_t *)(dq + 9);
     std::vector<int32_t> out(N);
     double qrow[9];
@@ -827,11 +668,12 @@ std::vector<int> PlannerClass::neighborhoodN(State q, int N) {  // :151-171
     chk(gbp_memcpy_h2d(dq, qrow, sizeof qrow, nullptr), "knn upload");
     if (cost_add_yaw_flag_) {
       sync_yaw();
-      chk(gbp_knn_yaw_batch_dev(1, dq, dq + 8, V, d_vertices_, d_yaw_, cost_add_yaw_length_weight_,
-                                cost_add_yaw_yaw_weight_, N, dout, nullptr, nullptr),
+      chk(gbp_knn_yaw_batch_dev(1, dq, dq + 8, V, dv, d_.yaw.data<double>(),
+                                cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_, N, dout, nullptr,
+                                nullptr),
           "neighborhoodN");
     } else {
-      chk(gbp_knn_batch_dev(1, dq, V, d_vertices_, N, dout, nullptr, nullptr), "neighborhoodN");
+      chk(gbp_knn_batch_dev(1, dq, V, dv, N, dout, nullptr, nullptr), "neighborhoodN");
     }
     chk(gbp_memcpy_d2h(out.data(), dout, (size_t)N * sizeof(int32_t), nullptr), "knn download");
     chk(gbp_stream_synchronize(nullptr), "knn sync");
@@ -865,6 +707,24 @@ gbp_sampling RRTClass::samplingConfig() const {
 void RRTClass::applySampling(FastTerrainMap &terrain) const {
   const gbp_sampling c = samplingConfig();
   chk(gbp_terrain_set_sampling(terrain.handle(), &c), "direction sampling");
+}
+
+void RRTClass::initTreePair(PlannerClass &Ta, PlannerClass &Tb, const State &s_start,
+                            const State &s_goal, uint64_t stream_a, uint64_t stream_b) const {
+  Ta.setStream(seed_, stream_a);
+  Tb.setStream(seed_, stream_b);
+  Ta.init(s_start, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
+  Tb.init(s_goal, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
+}
+
+void RRTClass::reportPath(JoinedPath &&path, std::vector<State> &state_sequence,
+                          std::vector<Action> &action_sequence) {
+  state_sequence = std::move(path.states);
+  action_sequence = std::move(path.actions);
+  path_length_ = path.length;
+  path_yaw_ = path.yaw;
+  path_cost_ = weightedCost(path_length_, path_yaw_);
+  path_duration_ = path.duration;
 }
 
 bool RRTClass::newConfig(State s, State s_near, State &s_new, Action &a_new, FastTerrainMap &terrain,
@@ -904,13 +764,7 @@ int RRTClass::extend(PlannerClass &T, State s, FastTerrainMap &terrain, int dire
 }
 
 std::vector<int> RRTClass::pathFromStart(PlannerClass &T, int s) {  // rrt.cpp:107-118
-  std::vector<int> path{s};
-  while (s != 0) {
-    s = T.getPredecessor(s);
-    path.push_back(s);
-  }
-  std::reverse(path.begin(), path.end());
-  return path;
+  return pathFromRoot(T.treeView().parent, s);
 }
 
 std::vector<State> RRTClass::getStateSequence(PlannerClass &T, std::vector<int> path) {
@@ -976,10 +830,10 @@ void RRTClass::print_setting_parameters() {
 // ============================================================================
 // RRTConnectClass
 // ============================================================================
-static void tree_extent(const PlannerClass &T, double e[4]) {
+static void tree_extent(const std::vector<State> &vertices, double e[4]) {
   e[0] = e[2] = INFINITY;
   e[1] = e[3] = -INFINITY;
-  for (const State &v : T.vertices()) {
+  for (const State &v : vertices) {
     e[0] = std::min(e[0], v[0]);
     e[1] = std::max(e[1], v[0]);
     e[2] = std::min(e[2], v[1]);
@@ -1193,12 +1047,23 @@ void RRTConnectClass::postProcessPath(std::vector<State> &state_sequence,
   action_sequence = new_actions;
 }
 
+bool RRTConnectClass::keepIfCheaper(std::vector<State> &state_sequence,
+                                    std::vector<Action> &action_sequence, FastTerrainMap &terrain,
+                                    double &cost_so_far) {
+  postProcessPath(state_sequence, action_sequence, terrain);  // :398, sets path_length_ / yaw / cost
+  if (!(path_cost_ < cost_so_far)) return false;              // :401-414
+  cost_so_far = path_cost_;
+  length_vector_.push_back(path_length_);
+  yaw_vector_.push_back(path_yaw_);
+  cost_vector_.push_back(path_cost_);
+  return true;
+}
+
 void RRTConnectClass::runRRTConnect(PlannerClass &Ta, PlannerClass &Tb,
                                     FastTerrainMap &terrain) {  // rrt_connect.cpp:230-314
-  const auto t_start = std::chrono::high_resolution_clock::now();
+  const Stopwatch clk;
   while (true) {
-    std::chrono::duration<double> el = std::chrono::high_resolution_clock::now() - t_start;
-    if (el.count() >= anytime_horizon) {
+    if (clk.seconds() >= anytime_horizon) {
       anytime_horizon = anytime_horizon * horizon_expansion_factor;
       return;
     }
@@ -1212,7 +1077,7 @@ void RRTConnectClass::runRRTConnect(PlannerClass &Ta, PlannerClass &Tb,
         const State s_new = Ta.getVertex(Ta.getNumVertices() - 1);
         if (connect(Tb, s_new, terrain, REVERSE) == GBP_PLANNER_REACHED) {
           goal_found = true;
-          elapsed_to_first = std::chrono::high_resolution_clock::now() - t_start;
+          elapsed_to_first = clk.elapsed();
           break;
         }
       }
@@ -1227,7 +1092,7 @@ void RRTConnectClass::runRRTConnect(PlannerClass &Ta, PlannerClass &Tb,
         const State s_new = Tb.getVertex(Tb.getNumVertices() - 1);
         if (connect(Ta, s_new, terrain, FORWARD) == GBP_PLANNER_REACHED) {
           goal_found = true;
-          elapsed_to_first = std::chrono::high_resolution_clock::now() - t_start;
+          elapsed_to_first = clk.elapsed();
           break;
         }
       }
@@ -1242,24 +1107,22 @@ void RRTConnectClass::buildRRTConnect(FastTerrainMap &terrain, State s_start, St
                                       std::vector<State> &state_sequence,
                                       std::vector<Action> &action_sequence,
                                       double max_time_opt) {  // rrt_connect.cpp:323-467
+  const Stopwatch clk;
+  success_ = 0;
   if (engine_batch_ > 0) {
     // the same restart loop (anytime horizons, post-processed solutions, the
     // cheapest kept, stop once one exists and max_time_opt has passed), each
     // restart's runRRTConnect run as the device-resident batched search
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    success_ = 0;
     BatchStats st;
     const bool found = buildRRTConnectBatchedAnytime(terrain, s_start, s_goal, engine_batch_,
                                                      max_time_solve, max_time_opt, state_sequence,
                                                      action_sequence, &st, true);
-    elapsed_total = std::chrono::high_resolution_clock::now() - t0;
+    elapsed_total = clk.elapsed();
     elapsed_to_first = std::chrono::duration<double>(wall_to_first_ >= 0 ? wall_to_first_ : 0.0);
     num_vertices = (int)(st.vertices_a + st.vertices_b);
     if (found && elapsed_total.count() <= 5.0) success_ = 1;  // :462-464
     return;
   }
-  const auto t_start = std::chrono::high_resolution_clock::now();
-  success_ = 0;
   length_vector_.clear();
   yaw_vector_.clear();
   cost_vector_.clear();
@@ -1270,21 +1133,24 @@ void RRTConnectClass::buildRRTConnect(FastTerrainMap &terrain, State s_start, St
       Tb_best(terrain.device());
   anytime_horizon = poseDistance(s_start, s_goal) / planning_rate_estimate;
   num_vertices = 0;
-  double length_so_far = INFTY, yaw_so_far = INFTY, cost_so_far = INFTY;
+  double cost_so_far = INFTY;
   int restart = 0;
+  auto joined = [&]() {  // rrt_connect.cpp:386-401, the trees' last vertices
+    JoinedPath p = joinTreePaths(Ta.treeView(), Ta.getNumVertices() - 1, Tb.treeView(),
+                                 Tb.getNumVertices() - 1);
+    state_sequence = std::move(p.states);
+    action_sequence = std::move(p.actions);
+  };
   std::chrono::duration<double> el{0};
   while (true) {
     Ta = PlannerClass(terrain.device());
     Tb = PlannerClass(terrain.device());
-    Ta.setStream(seed_, 1000 + 2 * restart);
-    Tb.setStream(seed_, 1001 + 2 * restart);
+    initTreePair(Ta, Tb, s_start, s_goal, 1000 + 2 * restart, 1001 + 2 * restart);
     restart++;
-    Ta.init(s_start, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
-    Tb.init(s_goal, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
     goal_found = false;
     runRRTConnect(Ta, Tb, terrain);
     num_vertices += Ta.getNumVertices() + Tb.getNumVertices();
-    el = std::chrono::high_resolution_clock::now() - t_start;
+    el = clk.elapsed();
     if (el.count() >= max_time_solve) {
       elapsed_total = el;
       elapsed_to_first = el;
@@ -1294,28 +1160,11 @@ void RRTConnectClass::buildRRTConnect(FastTerrainMap &terrain, State s_start, St
     }
     if (goal_found) {
       if (wall_to_first_ < 0) wall_to_first_ = el.count();
-      std::vector<int> path_a = pathFromStart(Ta, Ta.getNumVertices() - 1);
-      std::vector<int> path_b = pathFromStart(Tb, Tb.getNumVertices() - 1);
-      std::reverse(path_b.begin(), path_b.end());
-      std::vector<Action> action_sequence_b = getActionSequenceReverse(Tb, path_b);
-      path_b.erase(path_b.begin());
-      state_sequence = getStateSequence(Ta, path_a);
-      std::vector<State> sb = getStateSequence(Tb, path_b);
-      state_sequence.insert(state_sequence.end(), sb.begin(), sb.end());
-      action_sequence = getActionSequence(Ta, path_a);
-      action_sequence.insert(action_sequence.end(), action_sequence_b.begin(),
-                             action_sequence_b.end());
-      postProcessPath(state_sequence, action_sequence, terrain);
-      if (path_cost_ < cost_so_far) {
-        length_so_far = path_length_;
-        yaw_so_far = path_yaw_;
-        cost_so_far = path_cost_;
+      joined();
+      if (keepIfCheaper(state_sequence, action_sequence, terrain, cost_so_far)) {
         Ta_best = Ta;
         Tb_best = Tb;
-        el = std::chrono::high_resolution_clock::now() - t_start;
-        length_vector_.push_back(length_so_far);
-        yaw_vector_.push_back(yaw_so_far);
-        cost_vector_.push_back(cost_so_far);
+        el = clk.elapsed();
         cost_vector_times_.push_back(el.count());
       }
     }
@@ -1323,24 +1172,11 @@ void RRTConnectClass::buildRRTConnect(FastTerrainMap &terrain, State s_start, St
   }
   Ta = Ta_best;
   Tb = Tb_best;
-  if (goal_found) {
-    std::vector<int> path_a = pathFromStart(Ta, Ta.getNumVertices() - 1);
-    std::vector<int> path_b = pathFromStart(Tb, Tb.getNumVertices() - 1);
-    std::reverse(path_b.begin(), path_b.end());
-    std::vector<Action> action_sequence_b = getActionSequenceReverse(Tb, path_b);
-    path_b.erase(path_b.begin());
-    state_sequence = getStateSequence(Ta, path_a);
-    std::vector<State> sb = getStateSequence(Tb, path_b);
-    state_sequence.insert(state_sequence.end(), sb.begin(), sb.end());
-    action_sequence = getActionSequence(Ta, path_a);
-    action_sequence.insert(action_sequence.end(), action_sequence_b.begin(),
-                           action_sequence_b.end());
-  }
+  if (goal_found) joined();
   postProcessPath(state_sequence, action_sequence, terrain);
-  elapsed_total = std::chrono::high_resolution_clock::now() - t_start;
-  if (elapsed_total.count() <= 5.0) success_ = 1;
-  path_duration_ = 0.0;
-  for (const Action &a : action_sequence) path_duration_ += (a[6] + a[7]);
+  elapsed_total = clk.elapsed();
+  if (elapsed_total.count() <= 5.0) success_ = 1;  // success_ only within 5 s (:462-464)
+  path_duration_ = pathDuration(action_sequence);
 }
 
 // one batch-synchronous half-iteration: extend T toward `batch` targets, then
@@ -1483,21 +1319,17 @@ bool RRTConnectClass::buildRRTConnectBatched(FastTerrainMap &terrain, State s_st
                                              std::vector<State> &state_sequence,
                                              std::vector<Action> &action_sequence,
                                              BatchStats *stats) {
-  const auto t_start = std::chrono::high_resolution_clock::now();
+  const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
   PlannerClass Ta(terrain.device()), Tb(terrain.device());
-  Ta.setStream(seed_, 101);
-  Tb.setStream(seed_, 102);
-  Ta.init(s_start, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
-  Tb.init(s_goal, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
+  initTreePair(Ta, Tb, s_start, s_goal, 101, 102);
   BatchStats local;
   BatchStats &st = stats ? *stats : local;
   int ia = -1, ib = -1;
   auto more = [&]() { return st.max_halves <= 0 || st.halves < st.max_halves; };
   while (more()) {
-    std::chrono::duration<double> el = std::chrono::high_resolution_clock::now() - t_start;
-    if (el.count() >= max_time) break;
+    if (clk.seconds() >= max_time) break;
     st.iterations++;
     st.halves++;
     if (halfIterationBatched(Ta, Tb, terrain, FORWARD, batch, ia, ib, &st)) {
@@ -1511,9 +1343,9 @@ bool RRTConnectClass::buildRRTConnectBatched(FastTerrainMap &terrain, State s_st
       break;
     }
   }
-  elapsed_to_first = std::chrono::high_resolution_clock::now() - t_start;
-  tree_extent(Ta, st.extent_a);
-  tree_extent(Tb, st.extent_b);
+  elapsed_to_first = clk.elapsed();
+  tree_extent(Ta.vertices(), st.extent_a);
+  tree_extent(Tb.vertices(), st.extent_b);
   st.vertices_a = Ta.getNumVertices();
   st.vertices_b = Tb.getNumVertices();
   num_vertices = Ta.getNumVertices() + Tb.getNumVertices();
@@ -1523,21 +1355,7 @@ bool RRTConnectClass::buildRRTConnectBatched(FastTerrainMap &terrain, State s_st
   if (!goal_found) return false;
   wall_to_first_ = elapsed_to_first.count();
   // rrt_connect.cpp:386-401 with the meeting vertices (ia in Ta, ib in Tb)
-  std::vector<int> path_a = pathFromStart(Ta, ia);
-  std::vector<int> path_b = pathFromStart(Tb, ib);
-  std::reverse(path_b.begin(), path_b.end());
-  std::vector<Action> action_sequence_b = getActionSequenceReverse(Tb, path_b);
-  path_b.erase(path_b.begin());
-  state_sequence = getStateSequence(Ta, path_a);
-  std::vector<State> sb = getStateSequence(Tb, path_b);
-  state_sequence.insert(state_sequence.end(), sb.begin(), sb.end());
-  action_sequence = getActionSequence(Ta, path_a);
-  action_sequence.insert(action_sequence.end(), action_sequence_b.begin(), action_sequence_b.end());
-  path_length_ = Ta.getGValue(ia) + Tb.getGValue(ib);
-  path_yaw_ = Ta.getYValue(ia) + Tb.getYValue(ib);
-  path_cost_ = weightedCost(path_length_, path_yaw_);  // rrt_connect.cpp:304-313
-  path_duration_ = 0;
-  for (const Action &a : action_sequence) path_duration_ += a[6] + a[7];
+  reportPath(joinTreePaths(Ta.treeView(), ia, Tb.treeView(), ib), state_sequence, action_sequence);
   return true;
 }
 
@@ -1545,11 +1363,27 @@ bool RRTConnectClass::buildRRTConnectBatched(FastTerrainMap &terrain, State s_st
 // ---- the search resident on the device (include/gbp.h device planner loop) ----
 namespace {
 
-struct DeviceTrees {
+// One device-resident search: what it runs on, its trees, and where it stands.
+// RRT-Connect and RRT*-Connect drive it with their own outer loops.
+struct DeviceSearch {
+  gbp_terrain *h = nullptr;
+  int batch = 0, adaptive = 0;
+  uint64_t seed = 0, tstream[2] = {0, 0};  // the target streams, `batch` draws per half
+  // RRT*: the insertion stages (gbp_plan_star_config) with neighbourhood radius
+  // star_delta; warm starts load rewired trees instead of appending
+  bool star = false;
+  double star_delta = 0;
+  int64_t star_pairs_cap = 0;
   gbp_stream stream = nullptr;
   gbp_plan_ws *ws = nullptr;
   gbp_tree *tree[2] = {nullptr, nullptr};
-  ~DeviceTrees() {
+  int64_t known[2] = {1, 1};  // the trees' sizes when the last group ended
+  int32_t half0 = 0, half = 0;  // first half-iteration, next to run
+  // groups grow geometrically: a short search is not charged a long group's
+  // tail of gated half-iterations, a long one amortises the status read
+  int group = 2, g_max = 2;
+  gbp_plan_status ps{};
+  ~DeviceSearch() {
     if (stream) gbp_stream_synchronize(stream);
     for (gbp_tree *t : tree)
       if (t) gbp_tree_destroy(t);
@@ -1563,6 +1397,7 @@ struct HostTree {  // a device tree read back once the search ends
   std::vector<Action> a;
   std::vector<int32_t> parent;
   std::vector<double> g;
+  TreeView view() const { return {v.data(), a.data(), parent.data(), g.data()}; }
 };
 
 void read_tree(gbp_tree *t, gbp_stream s, HostTree &h) {
@@ -1576,32 +1411,145 @@ void read_tree(gbp_tree *t, gbp_stream s, HostTree &h) {
       "tree read");
 }
 
-std::vector<int> host_path(const HostTree &t, int idx) {  // rrt.cpp:107-118
-  std::vector<int> path{idx};
-  while (idx != 0) {
-    idx = t.parent[idx];
-    path.push_back(idx);
+// Both trees from their roots, or from a warm start (BatchStats::warm_*, a
+// replayable continuation): RRT-Connect appends the given vertices to the
+// root, RRT* loads the given trees, rewired parents included.
+void create_trees(DeviceSearch &S, int dev, const BatchStats &st, const State &s_start,
+                  const State &s_goal) {
+  const int64_t cap = std::max<int64_t>(1 << 16, 4 * (int64_t)S.batch);
+  for (int k = 0; k < 2; k++) {
+    const int64_t wn = st.warm_n[k];
+    if (wn > 0 && (!st.warm_v[k] || !st.warm_a[k] || !st.warm_parent[k] ||
+                   (!S.star && st.warm_parent[k][0] != -1)))
+      throw EngineError(GBP_E_INVALID_ARG, "warm start: tree arrays");
+    // an RRT-Connect tree: every vertex's parent was added before it (the
+    // oracle's warm start refuses anything else, orc_plan)
+    for (int64_t i = 1; !S.star && i < wn; i++)
+      if (st.warm_parent[k][i] < 0 || st.warm_parent[k][i] >= i)
+        throw EngineError(GBP_E_INVALID_ARG, "warm start: a parent after its child");
+    chk(gbp_tree_create(dev, std::max<int64_t>(cap, 2 * wn), &S.tree[k]), "tree");
+    const double *root = k == 0 ? s_start.data() : s_goal.data();
+    if (S.star && wn > 0) {
+      chk(gbp_tree_load_host(S.tree[k], wn, st.warm_v[k], st.warm_a[k], st.warm_parent[k], S.stream),
+          "warm start: tree load");
+    } else {
+      chk(gbp_tree_init(S.tree[k], wn > 0 ? st.warm_v[k] : root, S.stream), "tree init");
+      if (wn > 1)
+        chk(gbp_tree_append_host(S.tree[k], wn - 1, st.warm_v[k] + 8, st.warm_a[k] + 10,
+                                 st.warm_parent[k] + 1, S.stream),
+            "warm start: tree append");
+    }
+    S.known[k] = std::max<int64_t>(1, wn);
   }
-  std::reverse(path.begin(), path.end());
-  return path;
 }
 
-double path_yaw(const HostTree &t, const std::vector<int> &path) {
-  // y of the last vertex: updateGYValue's sums along the parent chain (rrt.cpp:91-92)
-  double y = 0;
-  for (size_t i = 1; i < path.size(); i++)
-    y = y + stateYawDistance(t.v[path[i - 1]], t.v[path[i]]);
-  return y;
+// Stream, workspace and trees of a search whose h, batch, adaptive, seed,
+// tstream and star fields are set; the candidate stream starts at
+// extend_counter, or at the warm start's extend index.
+void open_search(DeviceSearch &S, int dev, const BatchStats &st, const State &s_start,
+                 const State &s_goal, int64_t &extend_counter) {
+  chk(gbp_stream_create(dev, &S.stream), "stream");
+  chk(gbp_plan_ws_create(S.h, S.batch, &S.ws), "plan workspace");
+  if (S.star) {
+    // neighbour pairs of one half (2 connect checks each) and REACHED connections of the run
+    S.star_pairs_cap = std::max<int64_t>(1 << 18, 8 * (int64_t)S.batch);
+    chk(gbp_plan_star_config(S.ws, 1, S.star_delta, S.star_pairs_cap, 1 << 22), "star config");
+  }
+  if (st.stage_timing) chk(gbp_plan_stage_timing(S.ws, 1), "stage timing");
+  create_trees(S, dev, st, s_start, s_goal);
+  // RRT* runs pairs of half-iterations: its first half is even
+  if (st.warm_half < 0 || (S.star && (st.warm_half & 1)) || st.warm_extend < 0)
+    throw EngineError(GBP_E_INVALID_ARG, "warm start");
+  S.half = S.half0 = (int32_t)st.warm_half;
+  if (st.warm_n[0] > 0 || st.warm_n[1] > 0 || S.half0 > 0) extend_counter = st.warm_extend;
+  chk(gbp_plan_reset(S.ws, extend_counter, S.stream), "plan reset");
+  S.g_max = (int)std::max<int64_t>(2, std::min<int64_t>(64, (1 << 21) / S.batch)) & ~1;
 }
 
-void extent(const HostTree &t, double e[4]) {
-  e[0] = e[2] = INFINITY;
-  e[1] = e[3] = -INFINITY;
-  for (const State &v : t.v) {
-    e[0] = std::min(e[0], v[0]);
-    e[1] = std::max(e[1], v[0]);
-    e[2] = std::min(e[2], v[1]);
-    e[3] = std::max(e[3], v[1]);
+// The next S.group half-iterations (half h extends tree h % 2 toward its draws
+// [(h / 2) B, (h / 2 + 1) B)): room for their appends, one stream-ordered
+// kernel sequence, one status read; a FRAGILE halt is re-decided on the host
+// and the sequence resumed where it stopped.  Leaves the status in S.ps.
+void run_group(DeviceSearch &S, BatchStats &st) {
+  for (int k = 0; k < 2; k++) {  // room for `group` halves of appends
+    int64_t c = 0;
+    chk(gbp_tree_capacity(S.tree[k], &c), "tree capacity");
+    const int64_t need = S.known[k] + (int64_t)S.group * S.batch;
+    if (need > c)
+      chk(gbp_tree_reserve(S.tree[k], std::max<int64_t>(2 * c, need), S.stream), "tree reserve");
+  }
+  gbp_plan_status &ps = S.ps;
+  chk(gbp_plan_halves_dev(S.h, S.ws, S.tree[0], S.tree[1], S.half, S.group, S.batch, S.seed,
+                          S.tstream[0], S.tstream[1], S.adaptive, 0, S.stream),
+      "plan halves");
+  chk(gbp_plan_status_read(S.ws, &ps, S.stream), "plan status");
+  st.status_reads++;
+  while (ps.halt) {  // FRAGILE: re-decide on the host, resume where the sequence stopped
+    for (int b = 0; b < 4; b++) st.halts[b] += (ps.halt >> b) & 1u;
+    const int32_t h0 = ps.halt_half;
+    const int k = h0 & 1;
+    int resume = -1;
+    int64_t nres = 0;
+    if (S.star && (ps.halt & GBP_PLAN_HALT_STAR_PAIRS)) {
+      // a half's neighbour pairs outgrew the insertion sets: grow them (the
+      // run's kept connections stay) and redo the half's stage 6
+      st.star_grows++;
+      S.star_pairs_cap =
+          std::max<int64_t>(2 * S.star_pairs_cap, (int64_t)ps.star_pairs + ps.star_pairs / 4);
+      chk(gbp_plan_star_config(S.ws, 1, S.star_delta, S.star_pairs_cap, 1 << 22),
+          "star config (grow)");
+    }
+    chk(gbp_plan_resolve_host(S.h, S.ws, S.tree[k], S.tree[k ^ 1], k == 0 ? FORWARD : REVERSE,
+                              S.batch, S.adaptive, &resume, &nres, S.stream),
+        "plan resolve");
+    if (resume < 0) throw EngineError(GBP_E_INVALID_ARG, "plan resolve: nothing halted");
+    chk(gbp_plan_halves_dev(S.h, S.ws, S.tree[0], S.tree[1], h0, S.half + S.group - h0, S.batch,
+                            S.seed, S.tstream[0], S.tstream[1], S.adaptive, resume, S.stream),
+        "plan halves");
+    chk(gbp_plan_status_read(S.ws, &ps, S.stream), "plan status");
+    st.status_reads++;
+  }
+  if (ps.error & 1u) throw EngineError(GBP_E_HIP, "device planner loop: look-back spin exhausted");
+  if (S.star && (ps.error & 4u))
+    throw EngineError(GBP_E_SHAPE, "device RRT*: star workspace exhausted");
+  if (ps.error) throw EngineError(GBP_E_SHAPE, "device planner loop: a tree ran out of capacity");
+  for (int k = 0; k < 2; k++) chk(gbp_tree_size(S.tree[k], &S.known[k], S.stream), "tree size");
+  S.half += S.group;
+}
+
+// The end of a search: the stage times, the status counters both searches
+// share folded into st, and both trees read back (extents, sizes, dump).
+void close_search(DeviceSearch &S, BatchStats &st, HostTree &A, HostTree &B) {
+  const gbp_plan_status &ps = S.ps;
+  if (st.stage_timing) {
+    double us[7];
+    int64_t nh = 0;
+    chk(gbp_plan_stage_times(S.ws, us, 7, &nh, 1), "stage times");
+    for (int k = 0; k < 7; k++) st.stage_us[k] += us[k];
+    st.stage_halves += nh;
+  }
+  st.targets += ps.stat_targets;
+  st.extends += ps.stat_targets;
+  st.attempts_checked += ps.stat_attempts;
+  st.connects += ps.stat_added;
+  st.fragile_resolved += ps.stat_fragile_resolved;
+  st.depth_capped += ps.stat_depth_capped;
+  st.nn_rechecks += ps.stat_nn_rechecks;
+  st.nn_scans += ps.stat_nn_scans;
+  read_tree(S.tree[0], S.stream, A);
+  read_tree(S.tree[1], S.stream, B);
+  tree_extent(A.v, st.extent_a);
+  tree_extent(B.v, st.extent_b);
+  st.vertices_a = (int64_t)A.v.size();
+  st.vertices_b = (int64_t)B.v.size();
+  if (st.dump) {
+    const HostTree *t[2] = {&A, &B};
+    for (int k = 0; k < 2; k++) {
+      st.dump->v[k] = t[k]->v;
+      st.dump->a[k] = t[k]->a;
+      st.dump->parent[k] = t[k]->parent;
+      st.dump->g[k] = t[k]->g;
+    }
   }
 }
 
@@ -1613,55 +1561,22 @@ bool RRTConnectClass::buildRRTConnectDevice(FastTerrainMap &terrain, State s_sta
                                             std::vector<Action> &action_sequence,
                                             BatchStats *stats, uint64_t stream_a,
                                             uint64_t stream_b) {
-  const auto t_start = std::chrono::high_resolution_clock::now();
-  auto since = [&]() {
-    return std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t_start).count();
-  };
+  const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
   BatchStats local;
   BatchStats &st = stats ? *stats : local;
-  gbp_terrain *h = terrain.handle();
-  const int dev = terrain.device();
-  const int adaptive = state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0;
-  // the target streams (buildRRTConnectBatched's: Ta 101, Tb 102), B draws per half
-  const uint64_t tstream[2] = {stream_a, stream_b};
   applySampling(terrain);  // the device loop's targets and candidates read it from the handle
-  DeviceTrees D;
-  chk(gbp_stream_create(dev, &D.stream), "stream");
-  chk(gbp_plan_ws_create(h, batch, &D.ws), "plan workspace");
-  if (st.stage_timing) chk(gbp_plan_stage_timing(D.ws, 1), "stage timing");
-  int64_t cap = std::max<int64_t>(1 << 16, 4 * (int64_t)batch);
-  int64_t known[2] = {1, 1};
-  for (int k = 0; k < 2; k++) {
-    const int64_t wn = st.warm_n[k];
-    if (wn > 0 && (!st.warm_v[k] || !st.warm_a[k] || !st.warm_parent[k] || st.warm_parent[k][0] != -1))
-      throw EngineError(GBP_E_INVALID_ARG, "warm start: tree arrays");
-    // an RRT-Connect tree: every vertex's parent was added before it (the
-    // oracle's warm start refuses anything else, orc_plan)
-    for (int64_t i = 1; i < wn; i++)
-      if (st.warm_parent[k][i] < 0 || st.warm_parent[k][i] >= i)
-        throw EngineError(GBP_E_INVALID_ARG, "warm start: a parent after its child");
-    chk(gbp_tree_create(dev, std::max<int64_t>(cap, 2 * wn), &D.tree[k]), "tree");
-    const double *root = wn > 0 ? st.warm_v[k] : (k == 0 ? s_start.data() : s_goal.data());
-    chk(gbp_tree_init(D.tree[k], root, D.stream), "tree init");
-    if (wn > 1)
-      chk(gbp_tree_append_host(D.tree[k], wn - 1, st.warm_v[k] + 8, st.warm_a[k] + 10,
-                               st.warm_parent[k] + 1, D.stream),
-          "warm start: tree append");
-    known[k] = std::max<int64_t>(1, wn);
-  }
-  if (st.warm_half < 0 || st.warm_extend < 0) throw EngineError(GBP_E_INVALID_ARG, "warm start");
-  const int32_t half0 = (int32_t)st.warm_half;
-  if (st.warm_n[0] > 0 || st.warm_n[1] > 0 || half0 > 0) extend_counter_ = st.warm_extend;
-  chk(gbp_plan_reset(D.ws, extend_counter_, D.stream), "plan reset");
-  // half h extends tree h % 2 toward its draws [(h / 2) B, (h / 2 + 1) B)
-  // groups grow geometrically: a short search is not charged a long group's
-  // tail of gated half-iterations, a long one amortises the status read
-  const int g_max = (int)std::max<int64_t>(2, std::min<int64_t>(64, (1 << 21) / batch)) & ~1;
-  int group = 2;
-  int32_t half = half0;
-  gbp_plan_status ps{};
+  DeviceSearch S;
+  S.h = terrain.handle();
+  S.batch = batch;
+  S.adaptive = state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0;
+  S.seed = seed_;
+  // the target streams (buildRRTConnectBatched's: Ta 101, Tb 102)
+  S.tstream[0] = stream_a;
+  S.tstream[1] = stream_b;
+  open_search(S, terrain.device(), st, s_start, s_goal, extend_counter_);
+  const gbp_plan_status &ps = S.ps;
   // with a stop poll (config 4's restart trees, one per rank) the ranks stop
   // together: every group ends in one poll, and only its answer ends the loop
   bool go = max_time > 0;
@@ -1669,45 +1584,13 @@ bool RRTConnectClass::buildRRTConnectDevice(FastTerrainMap &terrain, State s_sta
   while (go) {
     bool local_stop = false;
     try {
-      if (st.max_halves > 0) group = (int)std::min<int64_t>(group, st.max_halves - (half - half0));
-      for (int k = 0; k < 2; k++) {  // room for `group` halves of appends
-        int64_t c = 0;
-        chk(gbp_tree_capacity(D.tree[k], &c), "tree capacity");
-        if (known[k] + (int64_t)group * batch > c)
-          chk(gbp_tree_reserve(D.tree[k], std::max<int64_t>(2 * c, known[k] + (int64_t)group * batch),
-                               D.stream),
-              "tree reserve");
-      }
-      // the group's halves, one stream-ordered kernel sequence
-      chk(gbp_plan_halves_dev(h, D.ws, D.tree[0], D.tree[1], half, group, batch, seed_, tstream[0],
-                              tstream[1], adaptive, 0, D.stream),
-          "plan halves");
-      chk(gbp_plan_status_read(D.ws, &ps, D.stream), "plan status");
-      st.status_reads++;
-      while (ps.halt) {  // FRAGILE: re-decide on the host, resume where the sequence stopped
-        for (int b = 0; b < 4; b++) st.halts[b] += (ps.halt >> b) & 1u;
-        const int32_t h0 = ps.halt_half;
-        const int k = h0 & 1;
-        int resume = -1;
-        int64_t nres = 0;
-        chk(gbp_plan_resolve_host(h, D.ws, D.tree[k], D.tree[k ^ 1], k == 0 ? FORWARD : REVERSE,
-                                  batch, adaptive, &resume, &nres, D.stream),
-            "plan resolve");
-        if (resume < 0) throw EngineError(GBP_E_INVALID_ARG, "plan resolve: nothing halted");
-        chk(gbp_plan_halves_dev(h, D.ws, D.tree[0], D.tree[1], h0, half + group - h0, batch, seed_,
-                                tstream[0], tstream[1], adaptive, resume, D.stream),
-            "plan halves");
-        chk(gbp_plan_status_read(D.ws, &ps, D.stream), "plan status");
-        st.status_reads++;
-      }
-      if (ps.error & 1u) throw EngineError(GBP_E_HIP, "device planner loop: look-back spin exhausted");
-      if (ps.error) throw EngineError(GBP_E_SHAPE, "device planner loop: a tree ran out of capacity");
-      for (int k = 0; k < 2; k++) chk(gbp_tree_size(D.tree[k], &known[k], D.stream), "tree size");
-      half += group;
+      if (st.max_halves > 0)
+        S.group = (int)std::min<int64_t>(S.group, st.max_halves - (S.half - S.half0));
+      run_group(S, st);
       if (ps.done) goal_found = true;
-      if (ps.done && t_first < 0) t_first = since();
-      local_stop = ps.done || since() >= max_time ||
-                   (st.max_halves > 0 && half - half0 >= st.max_halves);
+      if (ps.done && t_first < 0) t_first = clk.seconds();
+      local_stop = ps.done || clk.seconds() >= max_time ||
+                   (st.max_halves > 0 && S.half - S.half0 >= st.max_halves);
     } catch (...) {
       // the peers are (or will be) blocked in this group's poll: post a stop
       // so that their collective completes, then fail here
@@ -1724,46 +1607,16 @@ bool RRTConnectClass::buildRRTConnectDevice(FastTerrainMap &terrain, State s_sta
     } else {
       go = !local_stop;
     }
-    group = std::min(group * 2, g_max);
+    S.group = std::min(S.group * 2, S.g_max);
   }
-  elapsed_to_first = t_first >= 0 ? std::chrono::duration<double>(t_first)
-                                  : std::chrono::duration<double>(since());
+  elapsed_to_first = std::chrono::duration<double>(t_first >= 0 ? t_first : clk.seconds());
   extend_counter_ = ps.ext_counter;
-  if (st.stage_timing) {
-    double us[7];
-    int64_t nh = 0;
-    chk(gbp_plan_stage_times(D.ws, us, 7, &nh, 1), "stage times");
-    for (int k = 0; k < 7; k++) st.stage_us[k] += us[k];
-    st.stage_halves += nh;
-  }
-  const int32_t halves_run = (goal_found ? ps.meet_half + 1 : half) - half0;
+  const int32_t halves_run = (goal_found ? ps.meet_half + 1 : S.half) - S.half0;
   st.halves += halves_run;
   st.iterations += (halves_run + 1) / 2;
-  st.targets += ps.stat_targets;
-  st.extends += ps.stat_targets;
-  st.attempts_checked += ps.stat_attempts;
-  st.connects += ps.stat_added;
-  st.fragile_resolved += ps.stat_fragile_resolved;
-  st.depth_capped += ps.stat_depth_capped;
-  st.nn_rechecks += ps.stat_nn_rechecks;
-  st.nn_scans += ps.stat_nn_scans;
   HostTree A, B;
-  read_tree(D.tree[0], D.stream, A);
-  read_tree(D.tree[1], D.stream, B);
-  extent(A, st.extent_a);
-  extent(B, st.extent_b);
-  st.vertices_a = (int64_t)A.v.size();
-  st.vertices_b = (int64_t)B.v.size();
+  close_search(S, st, A, B);
   num_vertices = (int)(A.v.size() + B.v.size());
-  if (st.dump) {
-    const HostTree *t[2] = {&A, &B};
-    for (int k = 0; k < 2; k++) {
-      st.dump->v[k] = t[k]->v;
-      st.dump->a[k] = t[k]->a;
-      st.dump->parent[k] = t[k]->parent;
-      st.dump->g[k] = t[k]->g;
-    }
-  }
   if (!goal_found) return false;
   st.solutions++;
   wall_to_first_ = elapsed_to_first.count();
@@ -1772,28 +1625,11 @@ bool RRTConnectClass::buildRRTConnectDevice(FastTerrainMap &terrain, State s_sta
   const int32_t kconn = (int32_t)(ps.meet >> 32), o = (int32_t)(ps.meet & 0xFFFFFFFFu);
   const int32_t tvtx = ps.added_base + kconn;
   const bool t_is_a = (ps.meet_half & 1) == 0;
-  const int ia = t_is_a ? tvtx : o, ib = t_is_a ? o : tvtx;
-  st.meet_a = ia;
-  st.meet_b = ib;
+  st.meet_a = t_is_a ? tvtx : o;
+  st.meet_b = t_is_a ? o : tvtx;
   // rrt_connect.cpp:386-401 with the meeting vertices (as buildRRTConnectBatched)
-  std::vector<int> path_a = host_path(A, ia);
-  std::vector<int> path_b = host_path(B, ib);
-  std::reverse(path_b.begin(), path_b.end());
-  std::vector<Action> action_sequence_b;
-  for (size_t i = 0; i + 1 < path_b.size(); ++i) action_sequence_b.push_back(B.a[path_b[i]]);
-  const double yaw_b = path_yaw(B, host_path(B, ib));
-  path_b.erase(path_b.begin());
-  state_sequence.clear();
-  for (int i : path_a) state_sequence.push_back(A.v[i]);
-  for (int i : path_b) state_sequence.push_back(B.v[i]);
-  action_sequence.clear();
-  for (size_t i = 1; i < path_a.size(); ++i) action_sequence.push_back(A.a[path_a[i]]);
-  action_sequence.insert(action_sequence.end(), action_sequence_b.begin(), action_sequence_b.end());
-  path_length_ = A.g[ia] + B.g[ib];
-  path_yaw_ = path_yaw(A, path_a) + yaw_b;
-  path_cost_ = weightedCost(path_length_, path_yaw_);
-  path_duration_ = 0;
-  for (const Action &a : action_sequence) path_duration_ += a[6] + a[7];
+  reportPath(joinTreePaths(A.view(), st.meet_a, B.view(), st.meet_b), state_sequence,
+             action_sequence);
   return true;
 }
 
@@ -1803,10 +1639,7 @@ bool RRTConnectClass::buildRRTConnectBatchedAnytime(FastTerrainMap &terrain, Sta
                                                     std::vector<State> &state_sequence,
                                                     std::vector<Action> &action_sequence,
                                                     BatchStats *stats, bool device_loop) {
-  const auto t_start = std::chrono::high_resolution_clock::now();
-  auto since = [](std::chrono::high_resolution_clock::time_point t0) {
-    return std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-  };
+  const Stopwatch clk;
   BatchStats local;
   BatchStats &st = stats ? *stats : local;
   wall_to_first_ = -1;
@@ -1821,48 +1654,44 @@ bool RRTConnectClass::buildRRTConnectBatchedAnytime(FastTerrainMap &terrain, Sta
   std::vector<State> best_states;
   std::vector<Action> best_actions;
   double best_length = 0, best_yaw = 0;
+  // a restart's end at time el: keep its path if it is the cheapest; true = no further restart
+  auto settle = [&](bool found, std::vector<State> &states, std::vector<Action> &actions, double el) {
+    if (found) {
+      if (wall_to_first_ < 0) wall_to_first_ = el;
+      if (keepIfCheaper(states, actions, terrain, cost_so_far)) {
+        best_length = path_length_;
+        best_yaw = path_yaw_;
+        best_states = states;
+        best_actions = actions;
+        el = clk.seconds();
+        cost_vector_times_.push_back(el);
+      }
+      goal_found = true;
+    }
+    return (goal_found && el >= max_time_opt) ||  // :417
+           el >= max_time;                        // no (further) time: the best so far
+  };
   for (int restart = 0;; restart++) {  // :350-420, one pair of fresh trees per restart
+    std::vector<State> states;
+    std::vector<Action> actions;
     if (device_loop) {  // the restart's runRRTConnect as the device-resident search
-      const double budget = std::min(anytime_horizon, std::max(0.0, max_time - since(t_start)));
-      std::vector<State> states;
-      std::vector<Action> actions;
+      const double budget = std::min(anytime_horizon, std::max(0.0, max_time - clk.seconds()));
       const double w0 = wall_to_first_;
+      // (buildRRTConnectDevice counts the solution)
       const bool found = buildRRTConnectDevice(terrain, s_start, s_goal, batch, budget, states,
                                                actions, &st, 2000 + 2 * restart, 2001 + 2 * restart);
       wall_to_first_ = w0;
       if (!found) anytime_horizon *= horizon_expansion_factor;  // :238-242
-      double el = since(t_start);
-      if (found) {  // (buildRRTConnectDevice counted the solution)
-        if (wall_to_first_ < 0) wall_to_first_ = el;
-        postProcessPath(states, actions, terrain);  // :398
-        if (path_cost_ < cost_so_far) {             // :401-414
-          cost_so_far = path_cost_;
-          best_length = path_length_;
-          best_yaw = path_yaw_;
-          best_states = states;
-          best_actions = actions;
-          el = since(t_start);
-          length_vector_.push_back(best_length);
-          yaw_vector_.push_back(best_yaw);
-          cost_vector_.push_back(cost_so_far);
-          cost_vector_times_.push_back(el);
-        }
-        goal_found = true;
-      }
-      if (goal_found && el >= max_time_opt) break;
-      if (el >= max_time) break;
+      if (settle(found, states, actions, clk.seconds())) break;
       continue;
     }
     PlannerClass Ta(terrain.device()), Tb(terrain.device());
-    Ta.setStream(seed_, 2000 + 2 * restart);
-    Tb.setStream(seed_, 2001 + 2 * restart);
-    Ta.init(s_start, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
-    Tb.init(s_goal, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
-    const auto t_run = std::chrono::high_resolution_clock::now();
+    initTreePair(Ta, Tb, s_start, s_goal, 2000 + 2 * restart, 2001 + 2 * restart);
+    const Stopwatch run;
     bool found = false;
     int ia = -1, ib = -1;
     while (true) {  // runRRTConnect (:228-318) at batch granularity
-      if (since(t_run) >= anytime_horizon) {
+      if (run.seconds() >= anytime_horizon) {
         anytime_horizon *= horizon_expansion_factor;
         break;
       }
@@ -1872,56 +1701,30 @@ bool RRTConnectClass::buildRRTConnectBatchedAnytime(FastTerrainMap &terrain, Sta
         found = true;
         break;
       }
-      if (since(t_start) >= max_time) break;
+      if (clk.seconds() >= max_time) break;
     }
     num_vertices += Ta.getNumVertices() + Tb.getNumVertices();
     st.vertices_a = Ta.getNumVertices();
     st.vertices_b = Tb.getNumVertices();
-    tree_extent(Ta, st.extent_a);
-    tree_extent(Tb, st.extent_b);
-    double el = since(t_start);
+    tree_extent(Ta.vertices(), st.extent_a);
+    tree_extent(Tb.vertices(), st.extent_b);
+    const double el = clk.seconds();
     if (found) {
       st.solutions++;
-      if (wall_to_first_ < 0) wall_to_first_ = el;
-      std::vector<int> path_a = pathFromStart(Ta, ia);
-      std::vector<int> path_b = pathFromStart(Tb, ib);
-      std::reverse(path_b.begin(), path_b.end());
-      std::vector<Action> action_b = getActionSequenceReverse(Tb, path_b);
-      path_b.erase(path_b.begin());
-      std::vector<State> states = getStateSequence(Ta, path_a);
-      std::vector<State> sb = getStateSequence(Tb, path_b);
-      states.insert(states.end(), sb.begin(), sb.end());
-      std::vector<Action> actions = getActionSequence(Ta, path_a);
-      actions.insert(actions.end(), action_b.begin(), action_b.end());
-      path_length_ = Ta.getGValue(ia) + Tb.getGValue(ib);
-      path_yaw_ = Ta.getYValue(ia) + Tb.getYValue(ib);
-      postProcessPath(states, actions, terrain);  // :398, sets path_length_/path_cost_
-      if (path_cost_ < cost_so_far) {  // :401-414
-        cost_so_far = path_cost_;
-        best_length = path_length_;
-        best_yaw = path_yaw_;
-        best_states = states;
-        best_actions = actions;
-        el = since(t_start);
-        length_vector_.push_back(best_length);
-        yaw_vector_.push_back(best_yaw);
-        cost_vector_.push_back(cost_so_far);
-        cost_vector_times_.push_back(el);
-      }
-      goal_found = true;
+      JoinedPath p = joinTreePaths(Ta.treeView(), ia, Tb.treeView(), ib);
+      states = std::move(p.states);
+      actions = std::move(p.actions);
     }
-    if (goal_found && el >= max_time_opt) break;  // :417
-    if (el >= max_time) break;                     // no (further) time: the best so far
+    if (settle(found, states, actions, el)) break;
   }
-  elapsed_total = std::chrono::high_resolution_clock::now() - t_start;
+  elapsed_total = clk.elapsed();
   if (!goal_found) return false;
   state_sequence = best_states;
   action_sequence = best_actions;
   path_length_ = best_length;
   path_yaw_ = best_yaw;
   path_cost_ = cost_so_far;
-  path_duration_ = 0;
-  for (const Action &a : action_sequence) path_duration_ += a[6] + a[7];
+  path_duration_ = pathDuration(action_sequence);
   return true;
 }
 
@@ -2025,112 +1828,97 @@ void RRTStarConnectClass::getStateAndActionSequences(PlannerClass &Ta, PlannerCl
                                                      int shared_a_idx, int shared_b_idx,
                                                      std::vector<State> &state_sequence,
                                                      std::vector<Action> &action_sequence) {
-  state_sequence.clear();  // rrt_star_connect.cpp:70-89
-  action_sequence.clear();
-  std::vector<int> path_a = pathFromStart(Ta, shared_a_idx);
-  std::vector<int> path_b = pathFromStart(Tb, shared_b_idx);
-  std::reverse(path_b.begin(), path_b.end());
-  std::vector<Action> action_sequence_b = getActionSequenceReverse(Tb, path_b);
-  path_b.erase(path_b.begin());
-  state_sequence = getStateSequence(Ta, path_a);
-  std::vector<State> sb = getStateSequence(Tb, path_b);
-  state_sequence.insert(state_sequence.end(), sb.begin(), sb.end());
-  action_sequence = getActionSequence(Ta, path_a);
-  action_sequence.insert(action_sequence.end(), action_sequence_b.begin(), action_sequence_b.end());
+  // rrt_star_connect.cpp:70-89
+  JoinedPath p = joinTreePaths(Ta.treeView(), shared_a_idx, Tb.treeView(), shared_b_idx);
+  state_sequence = std::move(p.states);
+  action_sequence = std::move(p.actions);
+}
+
+// The connection (shared_a[i], shared_b[i]) with the lowest g_a + g_b below
+// cost_so_far becomes (best_a, best_b); improved() runs at every step down
+// (rrt_star_connect.cpp:175-195).  Rewiring keeps lowering g, so the searches
+// rank all connections again after every iteration.
+template <class Improved>
+static void rankSharedConnections(const PlannerClass &Ta, const PlannerClass &Tb,
+                                  const std::vector<int> &shared_a,
+                                  const std::vector<int> &shared_b, double &cost_so_far,
+                                  int &best_a, int &best_b, Improved improved) {
+  for (size_t i = 0; i < shared_a.size(); ++i) {
+    const double cost = Ta.getGValue(shared_a[i]) + Tb.getGValue(shared_b[i]);
+    if (cost < cost_so_far) {
+      cost_so_far = cost;
+      best_a = shared_a[i];
+      best_b = shared_b[i];
+      improved();
+    }
+  }
 }
 
 void RRTStarConnectClass::buildRRTStarConnect(FastTerrainMap &terrain, State s_start, State s_goal,
                                               std::vector<State> &state_sequence,
                                               std::vector<Action> &action_sequence,
                                               double max_time) {  // rrt_star_connect.cpp:91-205
-  const auto t_start = std::chrono::high_resolution_clock::now();
+  const Stopwatch clk;
   success_ = 0;
   length_vector_.clear();
   yaw_vector_.clear();
   cost_vector_.clear();
   cost_vector_times_.clear();
   PlannerClass Ta(terrain.device()), Tb(terrain.device());
-  Ta.setStream(seed_, 301);
-  Tb.setStream(seed_, 302);
-  Ta.init(s_start, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
-  Tb.init(s_goal, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
+  initTreePair(Ta, Tb, s_start, s_goal, 301, 302);
   int shared_a_idx = -1, shared_b_idx = -1;
   std::vector<int> shared_a, shared_b;
   goal_found = false;
   wall_to_first_ = -1;
   const double length_so_far = INFTY, yaw_so_far = INFTY;  // never updated by the reference
   double cost_so_far = INFTY;
+  auto reached = [&]() {  // a connect joined the trees at their last vertices
+    if (!goal_found) {
+      elapsed_to_first = clk.elapsed();
+      wall_to_first_ = elapsed_to_first.count();
+    }
+    goal_found = true;
+    shared_a.push_back(Ta.getNumVertices() - 1);
+    shared_b.push_back(Tb.getNumVertices() - 1);
+  };
   while (true) {
     State s_rand = Ta.randomState(terrain);
     if (isValidState(s_rand, terrain, STANCE)) {
       if (extend(Ta, s_rand, terrain, FORWARD) != GBP_PLANNER_TRAPPED) {
         const State s_new = Ta.getVertex(Ta.getNumVertices() - 1);
-        if (connect(Tb, s_new, terrain, REVERSE) == GBP_PLANNER_REACHED) {
-          if (!goal_found) {
-            elapsed_to_first = std::chrono::high_resolution_clock::now() - t_start;
-            wall_to_first_ = elapsed_to_first.count();
-          }
-          goal_found = true;
-          shared_a.push_back(Ta.getNumVertices() - 1);
-          shared_b.push_back(Tb.getNumVertices() - 1);
-        }
+        if (connect(Tb, s_new, terrain, REVERSE) == GBP_PLANNER_REACHED) reached();
       }
     }
     s_rand = Tb.randomState(terrain);
     if (isValidState(s_rand, terrain, STANCE)) {
       if (extend(Tb, s_rand, terrain, REVERSE) != GBP_PLANNER_TRAPPED) {
         const State s_new = Tb.getVertex(Tb.getNumVertices() - 1);
-        if (connect(Ta, s_new, terrain, FORWARD) == GBP_PLANNER_REACHED) {
-          if (!goal_found) {
-            elapsed_to_first = std::chrono::high_resolution_clock::now() - t_start;
-            wall_to_first_ = elapsed_to_first.count();
-          }
-          goal_found = true;
-          shared_a.push_back(Ta.getNumVertices() - 1);
-          shared_b.push_back(Tb.getNumVertices() - 1);
-        }
+        if (connect(Ta, s_new, terrain, FORWARD) == GBP_PLANNER_REACHED) reached();
       }
     }
-    const std::chrono::duration<double> el = std::chrono::high_resolution_clock::now() - t_start;
-    if (goal_found && el.count() >= max_time) break;
-    for (size_t i = 0; i < shared_a.size(); ++i) {
-      const double cost = Ta.getGValue(shared_a[i]) + Tb.getGValue(shared_b[i]);
-      if (cost < cost_so_far) {
-        cost_so_far = cost;
-        shared_a_idx = shared_a[i];
-        shared_b_idx = shared_b[i];
-        length_vector_.push_back(length_so_far);
-        yaw_vector_.push_back(yaw_so_far);
-        cost_vector_.push_back(cost_so_far);
-        cost_vector_times_.push_back(
-            std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t_start)
-                .count());
-      }
-    }
+    if (goal_found && clk.seconds() >= max_time) break;
+    rankSharedConnections(Ta, Tb, shared_a, shared_b, cost_so_far, shared_a_idx, shared_b_idx, [&]() {
+      length_vector_.push_back(length_so_far);
+      yaw_vector_.push_back(yaw_so_far);
+      cost_vector_.push_back(cost_so_far);
+      cost_vector_times_.push_back(clk.seconds());
+    });
   }
   // the reference leaves the loop before ranking a connection found in its last
   // iteration (shared_a_idx may then be uninitialised): rank once more
-  for (size_t i = 0; i < shared_a.size(); ++i) {
-    const double cost = Ta.getGValue(shared_a[i]) + Tb.getGValue(shared_b[i]);
-    if (cost < cost_so_far) {
-      cost_so_far = cost;
-      shared_a_idx = shared_a[i];
-      shared_b_idx = shared_b[i];
-    }
-  }
+  rankSharedConnections(Ta, Tb, shared_a, shared_b, cost_so_far, shared_a_idx, shared_b_idx, [] {});
   num_vertices = Ta.getNumVertices() + Tb.getNumVertices();
   if (goal_found && shared_a_idx >= 0)
     getStateAndActionSequences(Ta, Tb, shared_a_idx, shared_b_idx, state_sequence, action_sequence);
-  elapsed_total = std::chrono::high_resolution_clock::now() - t_start;
+  elapsed_total = clk.elapsed();
   length_vector_.push_back(length_so_far);
   yaw_vector_.push_back(yaw_so_far);
   cost_vector_.push_back(cost_so_far);
   cost_vector_times_.push_back(elapsed_total.count());
   best_cost_ = cost_so_far;
   if (!state_sequence.empty()) postProcessPath(state_sequence, action_sequence, terrain);
-  if (elapsed_total.count() <= 5.0) success_ = 1;
-  path_duration_ = 0.0;
-  for (const Action &a : action_sequence) path_duration_ += a[6] + a[7];
+  if (elapsed_total.count() <= 5.0) success_ = 1;  // success_ only within 5 s
+  path_duration_ = pathDuration(action_sequence);
 }
 
 bool RRTStarConnectClass::buildRRTStarConnectBatched(FastTerrainMap &terrain, State s_start,
@@ -2138,26 +1926,21 @@ bool RRTStarConnectClass::buildRRTStarConnectBatched(FastTerrainMap &terrain, St
                                                      std::vector<State> &state_sequence,
                                                      std::vector<Action> &action_sequence,
                                                      BatchStats *stats) {
-  const auto t_start = std::chrono::high_resolution_clock::now();
+  const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
   rewires_ = 0;
   cost_vector_.clear();
   cost_vector_times_.clear();
   PlannerClass Ta(terrain.device()), Tb(terrain.device());
-  Ta.setStream(seed_, 401);
-  Tb.setStream(seed_, 402);
-  Ta.init(s_start, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
-  Tb.init(s_goal, cost_add_yaw_flag_, cost_add_yaw_length_weight_, cost_add_yaw_yaw_weight_);
+  initTreePair(Ta, Tb, s_start, s_goal, 401, 402);
   BatchStats local;
   BatchStats &st = stats ? *stats : local;
   std::vector<int> shared_a, shared_b;
   int best_a = -1, best_b = -1;
   double cost_so_far = INFTY;
   while (st.max_halves <= 0 || st.halves + 2 <= st.max_halves) {
-    const double el =
-        std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t_start).count();
-    if (el >= max_time) break;
+    if (clk.seconds() >= max_time) break;
     st.iterations++;
     st.halves += 2;
     for (int half = 0; half < 2; half++) {
@@ -2170,7 +1953,7 @@ bool RRTStarConnectClass::buildRRTStarConnectBatched(FastTerrainMap &terrain, St
       insertStar(T, terrain, dir, added, nearest, a_new, &st);
       for (const auto &pr : connectBatch(T, O, terrain, dir, added, &st)) {
         if (!goal_found) {
-          elapsed_to_first = std::chrono::high_resolution_clock::now() - t_start;
+          elapsed_to_first = clk.elapsed();
           wall_to_first_ = elapsed_to_first.count();
         }
         goal_found = true;
@@ -2179,21 +1962,13 @@ bool RRTStarConnectClass::buildRRTStarConnectBatched(FastTerrainMap &terrain, St
         st.solutions++;
       }
     }
-    for (size_t i = 0; i < shared_a.size(); ++i) {  // rewiring keeps lowering g
-      const double cost = Ta.getGValue(shared_a[i]) + Tb.getGValue(shared_b[i]);
-      if (cost < cost_so_far) {
-        cost_so_far = cost;
-        best_a = shared_a[i];
-        best_b = shared_b[i];
-        cost_vector_.push_back(cost_so_far);
-        cost_vector_times_.push_back(
-            std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t_start)
-                .count());
-      }
-    }
+    rankSharedConnections(Ta, Tb, shared_a, shared_b, cost_so_far, best_a, best_b, [&]() {
+      cost_vector_.push_back(cost_so_far);
+      cost_vector_times_.push_back(clk.seconds());
+    });
   }
-  tree_extent(Ta, st.extent_a);
-  tree_extent(Tb, st.extent_b);
+  tree_extent(Ta.vertices(), st.extent_a);
+  tree_extent(Tb.vertices(), st.extent_b);
   st.vertices_a = Ta.getNumVertices();
   st.vertices_b = Tb.getNumVertices();
   num_vertices = Ta.getNumVertices() + Tb.getNumVertices();
@@ -2202,12 +1977,8 @@ bool RRTStarConnectClass::buildRRTStarConnectBatched(FastTerrainMap &terrain, St
   st.meet_a = best_a;
   st.meet_b = best_b;
   if (!goal_found) return false;
-  getStateAndActionSequences(Ta, Tb, best_a, best_b, state_sequence, action_sequence);
-  path_length_ = Ta.getGValue(best_a) + Tb.getGValue(best_b);
-  path_yaw_ = Ta.getYValue(best_a) + Tb.getYValue(best_b);
-  path_cost_ = weightedCost(path_length_, path_yaw_);
-  path_duration_ = 0;
-  for (const Action &a : action_sequence) path_duration_ += a[6] + a[7];
+  reportPath(joinTreePaths(Ta.treeView(), best_a, Tb.treeView(), best_b), state_sequence,
+             action_sequence);
   return true;
 }
 
@@ -2216,10 +1987,7 @@ bool RRTStarConnectClass::buildRRTStarConnectDevice(FastTerrainMap &terrain, Sta
                                                     std::vector<State> &state_sequence,
                                                     std::vector<Action> &action_sequence,
                                                     BatchStats *stats) {
-  const auto t_start = std::chrono::high_resolution_clock::now();
-  auto since = [&]() {
-    return std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t_start).count();
-  };
+  const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
   rewires_ = 0;
@@ -2227,162 +1995,55 @@ bool RRTStarConnectClass::buildRRTStarConnectDevice(FastTerrainMap &terrain, Sta
   cost_vector_times_.clear();
   BatchStats local;
   BatchStats &st = stats ? *stats : local;
-  gbp_terrain *h = terrain.handle();
-  const int dev = terrain.device();
-  const int adaptive = state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0;
   // RRT*'s targets are plain randomState draws (extendBatch without O); the
   // candidates keep the action sampling (rrt.cpp:34, :49)
   gbp_sampling cfg = samplingConfig();
   cfg.state_flag = 0;
-  chk(gbp_terrain_set_sampling(h, &cfg), "sampling");
-  DeviceTrees D;
-  chk(gbp_stream_create(dev, &D.stream), "stream");
-  chk(gbp_plan_ws_create(h, batch, &D.ws), "plan workspace");
-  // neighbour pairs of one half (2 connect checks each) and REACHED connections of the run
-  int64_t star_pairs_cap = std::max<int64_t>(1 << 18, 8 * (int64_t)batch);
-  chk(gbp_plan_star_config(D.ws, 1, delta, star_pairs_cap, 1 << 22), "star config");
-  if (st.stage_timing) chk(gbp_plan_stage_timing(D.ws, 1), "stage timing");
-  int64_t cap = std::max<int64_t>(1 << 16, 4 * (int64_t)batch);
-  int64_t known[2] = {1, 1};
-  for (int k = 0; k < 2; k++) {
-    // warm start (a replayable continuation): the given trees, rewired parents included
-    const int64_t wn = st.warm_n[k];
-    if (wn > 0 && (!st.warm_v[k] || !st.warm_a[k] || !st.warm_parent[k]))
-      throw EngineError(GBP_E_INVALID_ARG, "warm start: tree arrays");
-    chk(gbp_tree_create(dev, std::max<int64_t>(cap, 2 * wn), &D.tree[k]), "tree");
-    if (wn > 0)
-      chk(gbp_tree_load_host(D.tree[k], wn, st.warm_v[k], st.warm_a[k], st.warm_parent[k], D.stream),
-          "warm start: tree load");
-    else
-      chk(gbp_tree_init(D.tree[k], k == 0 ? s_start.data() : s_goal.data(), D.stream), "tree init");
-    known[k] = std::max<int64_t>(1, wn);
-  }
-  if (st.warm_half < 0 || (st.warm_half & 1) || st.warm_extend < 0)
-    throw EngineError(GBP_E_INVALID_ARG, "warm start");
-  const int32_t half0 = (int32_t)st.warm_half;
-  if (st.warm_n[0] > 0 || st.warm_n[1] > 0 || half0 > 0) extend_counter_ = st.warm_extend;
-  chk(gbp_plan_reset(D.ws, extend_counter_, D.stream), "plan reset");
-  const uint64_t tstream[2] = {401, 402};  // buildRRTStarConnectBatched's streams
-  const int g_max = (int)std::max<int64_t>(2, std::min<int64_t>(64, (1 << 21) / batch)) & ~1;
-  int group = 2;
-  int32_t half = half0;
-  gbp_plan_status ps{};
-  while (since() < max_time && (st.max_halves <= 0 || half - half0 + 2 <= st.max_halves)) {
+  chk(gbp_terrain_set_sampling(terrain.handle(), &cfg), "sampling");
+  DeviceSearch S;
+  S.h = terrain.handle();
+  S.batch = batch;
+  S.adaptive = state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0;
+  S.seed = seed_;
+  S.tstream[0] = 401;  // buildRRTStarConnectBatched's streams
+  S.tstream[1] = 402;
+  S.star = true;
+  S.star_delta = delta;
+  open_search(S, terrain.device(), st, s_start, s_goal, extend_counter_);
+  const gbp_plan_status &ps = S.ps;
+  while (clk.seconds() < max_time &&
+         (st.max_halves <= 0 || S.half - S.half0 + 2 <= st.max_halves)) {
     if (st.max_halves > 0)
-      group = (int)std::min<int64_t>(group, (st.max_halves - (half - half0)) & ~1LL);
-    for (int k = 0; k < 2; k++) {
-      int64_t c = 0;
-      chk(gbp_tree_capacity(D.tree[k], &c), "tree capacity");
-      if (known[k] + (int64_t)group * batch > c)
-        chk(gbp_tree_reserve(D.tree[k], std::max<int64_t>(2 * c, known[k] + (int64_t)group * batch),
-                             D.stream),
-            "tree reserve");
-    }
-    chk(gbp_plan_halves_dev(h, D.ws, D.tree[0], D.tree[1], half, group, batch, seed_, tstream[0],
-                            tstream[1], adaptive, 0, D.stream),
-        "plan halves");
-    chk(gbp_plan_status_read(D.ws, &ps, D.stream), "plan status");
-    st.status_reads++;
-    while (ps.halt) {  // FRAGILE: re-decide on the host, resume where the sequence stopped
-      for (int b = 0; b < 4; b++) st.halts[b] += (ps.halt >> b) & 1u;
-      const int32_t h0 = ps.halt_half;
-      const int k = h0 & 1;
-      int resume = -1;
-      int64_t nres = 0;
-      if (ps.halt & GBP_PLAN_HALT_STAR_PAIRS) {
-        // a half's neighbour pairs outgrew the insertion sets: grow them (the
-        // run's kept connections stay) and redo the half's stage 6
-        st.star_grows++;
-        star_pairs_cap = std::max<int64_t>(2 * star_pairs_cap, (int64_t)ps.star_pairs + ps.star_pairs / 4);
-        chk(gbp_plan_star_config(D.ws, 1, delta, star_pairs_cap, 1 << 22), "star config (grow)");
-      }
-      chk(gbp_plan_resolve_host(h, D.ws, D.tree[k], D.tree[k ^ 1], k == 0 ? FORWARD : REVERSE,
-                                batch, adaptive, &resume, &nres, D.stream),
-          "plan resolve");
-      if (resume < 0) throw EngineError(GBP_E_INVALID_ARG, "plan resolve: nothing halted");
-      chk(gbp_plan_halves_dev(h, D.ws, D.tree[0], D.tree[1], h0, half + group - h0, batch, seed_,
-                              tstream[0], tstream[1], adaptive, resume, D.stream),
-          "plan halves");
-      chk(gbp_plan_status_read(D.ws, &ps, D.stream), "plan status");
-      st.status_reads++;
-    }
-    if (ps.error & 1u) throw EngineError(GBP_E_HIP, "device planner loop: look-back spin exhausted");
-    if (ps.error & 4u) throw EngineError(GBP_E_SHAPE, "device RRT*: star workspace exhausted");
-    if (ps.error) throw EngineError(GBP_E_SHAPE, "device planner loop: a tree ran out of capacity");
-    for (int k = 0; k < 2; k++) chk(gbp_tree_size(D.tree[k], &known[k], D.stream), "tree size");
-    half += group;
+      S.group = (int)std::min<int64_t>(S.group, (st.max_halves - (S.half - S.half0)) & ~1LL);
+    run_group(S, st);
     if (ps.n_shared > 0 && !goal_found) {
       goal_found = true;
-      elapsed_to_first = std::chrono::duration<double>(since());
+      elapsed_to_first = clk.elapsed();
       wall_to_first_ = elapsed_to_first.count();
     }
     if (ps.best_a >= 0 && (cost_vector_.empty() || ps.best_cost < cost_vector_.back())) {
       cost_vector_.push_back(ps.best_cost);  // the best so far, once per group
-      cost_vector_times_.push_back(since());
+      cost_vector_times_.push_back(clk.seconds());
     }
-    group = std::min(group * 2, g_max);
+    S.group = std::min(S.group * 2, S.g_max);
   }
   extend_counter_ = ps.ext_counter;
   rewires_ = ps.stat_rewires;
-  if (st.stage_timing) {
-    double us[7];
-    int64_t nh = 0;
-    chk(gbp_plan_stage_times(D.ws, us, 7, &nh, 1), "stage times");
-    for (int k = 0; k < 7; k++) st.stage_us[k] += us[k];
-    st.stage_halves += nh;
-  }
-  st.halves += half - half0;
-  st.iterations += (half - half0) / 2;
-  st.targets += ps.stat_targets;
-  st.extends += ps.stat_targets;
-  st.attempts_checked += ps.stat_attempts;
-  st.connects += ps.stat_added + ps.stat_star_connects;
+  st.halves += S.half - S.half0;
+  st.iterations += (S.half - S.half0) / 2;
+  st.connects += ps.stat_star_connects;
   st.rewires += ps.stat_rewires;
   st.solutions += ps.n_shared;
-  st.fragile_resolved += ps.stat_fragile_resolved;
-  st.depth_capped += ps.stat_depth_capped;
-  st.nn_rechecks += ps.stat_nn_rechecks;
-  st.nn_scans += ps.stat_nn_scans;
   HostTree A, B;
-  read_tree(D.tree[0], D.stream, A);
-  read_tree(D.tree[1], D.stream, B);
-  extent(A, st.extent_a);
-  extent(B, st.extent_b);
-  st.vertices_a = (int64_t)A.v.size();
-  st.vertices_b = (int64_t)B.v.size();
+  close_search(S, st, A, B);
   num_vertices = (int)(A.v.size() + B.v.size());
-  if (st.dump) {
-    const HostTree *t[2] = {&A, &B};
-    for (int k = 0; k < 2; k++) {
-      st.dump->v[k] = t[k]->v;
-      st.dump->a[k] = t[k]->a;
-      st.dump->parent[k] = t[k]->parent;
-      st.dump->g[k] = t[k]->g;
-    }
-  }
   best_cost_ = ps.best_a >= 0 ? ps.best_cost : INFINITY_COST;
   st.meet_a = ps.best_a;
   st.meet_b = ps.best_b;
   if (!goal_found || ps.best_a < 0) return false;
   // rrt_star_connect.cpp:70-89 on the device trees
-  std::vector<int> path_a = host_path(A, ps.best_a);
-  std::vector<int> path_b = host_path(B, ps.best_b);
-  std::reverse(path_b.begin(), path_b.end());
-  std::vector<Action> action_sequence_b;
-  for (size_t i = 0; i + 1 < path_b.size(); ++i) action_sequence_b.push_back(B.a[path_b[i]]);
-  const double yaw_b = path_yaw(B, host_path(B, ps.best_b));
-  path_b.erase(path_b.begin());
-  state_sequence.clear();
-  for (int i : path_a) state_sequence.push_back(A.v[i]);
-  for (int i : path_b) state_sequence.push_back(B.v[i]);
-  action_sequence.clear();
-  for (size_t i = 1; i < path_a.size(); ++i) action_sequence.push_back(A.a[path_a[i]]);
-  action_sequence.insert(action_sequence.end(), action_sequence_b.begin(), action_sequence_b.end());
-  path_length_ = A.g[ps.best_a] + B.g[ps.best_b];
-  path_yaw_ = path_yaw(A, path_a) + yaw_b;
-  path_cost_ = weightedCost(path_length_, path_yaw_);
-  path_duration_ = 0;
-  for (const Action &a : action_sequence) path_duration_ += a[6] + a[7];
+  reportPath(joinTreePaths(A.view(), ps.best_a, B.view(), ps.best_b), state_sequence,
+             action_sequence);
   return true;
 }
 
@@ -2439,7 +2100,7 @@ extern "C" int gbp_plan_rrt_connect(const gbp_plan_params *p, gbp_plan_result *r
       return GBP_E_INVALID_ARG;
     }
     if (p->tree_capacity > 0) st.dump = &dump;
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const Stopwatch clk;
     const bool found =
         p->algorithm == 1
             ? planner.buildRRTStarConnectBatched(terrain, s0, s1, p->batch, p->max_time, states,
@@ -2462,11 +2123,11 @@ extern "C" int gbp_plan_rrt_connect(const gbp_plan_params *p, gbp_plan_result *r
     // algorithm 2 / 4's paths are post-processed inside the restarts (as buildRRTConnect)
     if (found && p->post_process && p->algorithm != 2 && p->algorithm != 4)
       planner.postProcessPath(states, actions, terrain);
-    const std::chrono::duration<double> tot = std::chrono::high_resolution_clock::now() - t0;
+    const double total_time = clk.seconds();
     memset(r, 0, sizeof(*r));
     r->found = found ? 1 : 0;
     r->time_to_first = found ? ttf : -1.0;
-    r->total_time = tot.count();
+    r->total_time = total_time;
     r->iterations = st.iterations;
     r->targets = st.targets;
     r->extends = st.extends;
@@ -2511,9 +2172,7 @@ extern "C" int gbp_plan_rrt_connect(const gbp_plan_params *p, gbp_plan_result *r
       for (size_t i = 1; i < states.size(); i++) len += planning_utils::poseDistance(states[i - 1], states[i]);
       r->path_length = len;
       r->path_cost = (p->algorithm == 1 || p->algorithm == 5) ? planner.bestCost() : planner.pathCost();
-      double dur = 0;
-      for (const Action &a : actions) dur += a[6] + a[7];
-      r->path_duration = dur;
+      r->path_duration = pathDuration(actions);
       for (int i = 0; i < std::min<int>(capacity, (int)states.size()); i++) {
         if (path_states) std::copy(states[i].begin(), states[i].end(), path_states + 8 * i);
         if (path_actions && i < (int)actions.size())

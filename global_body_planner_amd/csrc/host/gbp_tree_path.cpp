@@ -1,0 +1,53 @@
+// gbp_tree_path.cpp — see gbp_tree_path.h.  Built with the host planner's flags
+// (-ffp-contract=off): the sums are the reference's, term by term.
+#include "gbp_tree_path.h"
+
+#include <algorithm>
+
+namespace gbp_amd {
+
+using planning_utils::stateYawDistance;
+
+std::vector<int> pathFromRoot(const int *parent, int idx) {
+  std::vector<int> path{idx};
+  while (idx != 0) {
+    idx = parent[idx];
+    path.push_back(idx);
+  }
+  std::reverse(path.begin(), path.end());
+  return path;
+}
+
+double pathDuration(const std::vector<Action> &actions) {
+  double duration = 0;
+  for (const Action &a : actions) duration += a[6] + a[7];
+  return duration;
+}
+
+// y of the path's last vertex: updateGYValue's sums along the parent chain
+// (rrt.cpp:91-92, graph_class.cpp:131-138)
+static double chainYaw(const TreeView &T, const std::vector<int> &path) {
+  double y = 0;
+  for (size_t i = 1; i < path.size(); i++) y = y + stateYawDistance(T.v[path[i - 1]], T.v[path[i]]);
+  return y;
+}
+
+JoinedPath joinTreePaths(const TreeView &Ta, int ia, const TreeView &Tb, int ib) {
+  const std::vector<int> path_a = pathFromRoot(Ta.parent, ia);
+  const std::vector<int> path_b = pathFromRoot(Tb.parent, ib);
+  JoinedPath p;
+  for (int i : path_a) p.states.push_back(Ta.v[i]);
+  for (size_t i = 1; i < path_a.size(); i++) p.actions.push_back(Ta.a[path_a[i]]);
+  // Tb from ib back to its root: ib's state is dropped (the connect put it at
+  // ia's), its action leads on to its parent
+  for (size_t i = path_b.size(); i-- > 1;) {
+    p.actions.push_back(Tb.a[path_b[i]]);
+    p.states.push_back(Tb.v[path_b[i - 1]]);
+  }
+  p.length = Ta.g[ia] + Tb.g[ib];
+  p.yaw = chainYaw(Ta, path_a) + chainYaw(Tb, path_b);
+  p.duration = pathDuration(p.actions);
+  return p;
+}
+
+}  // namespace gbp_amd

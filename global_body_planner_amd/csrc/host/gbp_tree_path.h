@@ -1,0 +1,41 @@
+// gbp_tree_path.h — the path through two half trees joined at a connection
+// (rrt_connect.cpp:386-401, rrt_star_connect.cpp:70-89).  Pure host code with
+// no engine call: every search form (PlannerClass trees on the host, trees
+// read back from the device) builds its path here.
+#pragma once
+
+#include <vector>
+
+#include "gbp_planner.h"
+
+namespace gbp_amd {
+
+// A read-only view of one tree, root at index 0: vertex states, the action
+// reaching each vertex, parents (root -1) and g (path length from the root).
+struct TreeView {
+  const State *v;
+  const Action *a;
+  const int *parent;
+  const double *g;
+};
+
+struct JoinedPath {
+  std::vector<State> states;
+  std::vector<Action> actions;
+  double length = 0;    // g_a[ia] + g_b[ib]
+  double yaw = 0;       // the two chains' yaw sums (what updateGYValue keeps in y)
+  double duration = 0;  // pathDuration(actions)
+};
+
+// rrt.cpp:107-118: the vertices root -> idx
+std::vector<int> pathFromRoot(const int *parent, int idx);
+
+// sum of stance + flight time over the actions
+double pathDuration(const std::vector<Action> &actions);
+
+// Ta's root -> ia, then Tb's ib -> root without ib itself; Tb's edges are
+// walked against their direction, so edge (parent <- child) carries the
+// child's action (getActionSequenceReverse).
+JoinedPath joinTreePaths(const TreeView &Ta, int ia, const TreeView &Tb, int ib);
+
+}  // namespace gbp_amd

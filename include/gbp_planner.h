@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gbp.h"
@@ -214,15 +215,38 @@ void getInterpPath(std::vector<State> state_sequence, std::vector<Action> action
                    std::vector<int> &interp_phase);
 }  // namespace planning_utils
 
+struct TreeView;  // csrc/host/gbp_tree_path.h
+struct JoinedPath;
+
+// A device allocation owned by its holder (gbp_device_alloc / gbp_device_free):
+// move-only, freed in the destructor.
+class DeviceBuffer {
+ public:
+  DeviceBuffer() = default;
+  DeviceBuffer(DeviceBuffer &&o) noexcept { *this = std::move(o); }
+  DeviceBuffer &operator=(DeviceBuffer &&o) noexcept;
+  DeviceBuffer(const DeviceBuffer &) = delete;
+  DeviceBuffer &operator=(const DeviceBuffer &) = delete;
+  ~DeviceBuffer();
+  // room for n elements of elem_bytes: a new allocation of max(min_elems,
+  // capacity) elements doubled until n fit, holding nothing valid (valid = 0)
+  void reserve(int device, int64_t n, size_t elem_bytes, int64_t min_elems, const char *what);
+  template <class T = void>
+  T *data() const { return static_cast<T *>(p_); }
+  int64_t capacity() const { return cap_; }
+  int64_t valid = 0;  // leading elements that hold the holder's current data
+
+ private:
+  void *p_ = nullptr;
+  int64_t cap_ = 0;
+};
+
 // ---- GraphClass + PlannerClass (graph_class.h, planner_class.h) --------------
 // Vertices live in host vectors AND in a device mirror (flat double[V][8]) that
 // the nearest-neighbour kernel scans.
 class PlannerClass {
  public:
   explicit PlannerClass(int device = 0);
-  ~PlannerClass();
-  PlannerClass(const PlannerClass &o);
-  PlannerClass &operator=(const PlannerClass &o);
 
   void init(State s, bool cost_add_yaw_flag = false, double cost_add_yaw_length_weight = 1,
             double cost_add_yaw_yaw_weight = 1);                           // graph_class.cpp:141-152
@@ -271,6 +295,8 @@ class PlannerClass {
     stream_id_ = stream_id;
   }
   const std::vector<State> &vertices() const { return vertices_; }
+  // the host arrays as the path join reads them (csrc/host/gbp_tree_path.h)
+  TreeView treeView() const;
 
  private:
   void sync_device();
@@ -284,14 +310,19 @@ class PlannerClass {
   std::vector<double> g_, y_;
   bool cost_add_yaw_flag_ = false;
   double cost_add_yaw_length_weight_ = 1, cost_add_yaw_yaw_weight_ = 1;
-  double *d_vertices_ = nullptr;
-  int64_t d_capacity_ = 0, d_count_ = 0;
-  void *d_scratch_ = nullptr;   // nearest-neighbour queries [q][8] + indices [q]
-  int64_t d_scratch_cap_ = 0;
-  void *d_nbr_ = nullptr;       // neighbourhood queries + output lists
-  size_t d_nbr_bytes_ = 0;
-  double *d_yaw_ = nullptr;     // atan2(v[4], v[3]) per vertex (glibc), uploaded on demand
-  int64_t d_yaw_cap_ = 0, d_yaw_count_ = 0;
+  // The device side is a cache of the host vectors, refilled on demand: a
+  // copy of a tree starts without one.
+  struct Mirror {
+    DeviceBuffer vertices;  // [V][8]
+    DeviceBuffer yaw;       // atan2(v[4], v[3]) per vertex (glibc), uploaded on demand
+    DeviceBuffer scratch;   // nearest-neighbour queries [q][8] + indices [q]
+    DeviceBuffer nbr;       // neighbourhood queries + output lists (bytes)
+    Mirror() = default;
+    Mirror(Mirror &&) = default;
+    Mirror &operator=(Mirror &&) = default;
+    Mirror(const Mirror &) {}
+    Mirror &operator=(const Mirror &o) { return this == &o ? *this : *this = Mirror(); }
+  } d_;
   uint64_t seed_ = 1, stream_id_ = 100;
   int64_t draws_ = 0;
 };
@@ -361,6 +392,14 @@ class RRTClass {
   // installs samplingConfig() on the terrain handle (the candidate sampler and
   // the device loop's targets read it there)
   void applySampling(FastTerrainMap &terrain) const;
+  // a search's two trees from their roots: Ta at s_start drawing from Philox
+  // stream stream_a of this planner's seed, Tb at s_goal from stream_b
+  void initTreePair(PlannerClass &Ta, PlannerClass &Tb, const State &s_start, const State &s_goal,
+                    uint64_t stream_a, uint64_t stream_b) const;
+  // hands out a search's joined path and reports its length, yaw, cost
+  // (rrt_connect.cpp:304-313) and duration
+  void reportPath(JoinedPath &&path, std::vector<State> &state_sequence,
+                  std::vector<Action> &action_sequence);
   bool goal_found = false;
   std::chrono::duration<double> elapsed_total{0};
   std::chrono::duration<double> elapsed_to_first{0};
@@ -520,6 +559,13 @@ class RRTConnectClass : public RRTClass {
   const int max_time_solve = 4000;
   int engine_batch_ = 1024;
   bool post_process_device_ = false;
+
+  // rrt_connect.cpp:398-414: post-process a found path and, when it is cheaper
+  // than cost_so_far, make it the new cost_so_far and add it to the length /
+  // yaw / cost histories.  Returns whether it was kept; the caller then stores
+  // its best and pushes the time into cost_vector_times_.
+  bool keepIfCheaper(std::vector<State> &state_sequence, std::vector<Action> &action_sequence,
+                     FastTerrainMap &terrain, double &cost_so_far);
 
   // lock-step attemptConnect for many (s_existing, s, t_s) triples; with
   // max_depth = 0 only REACHED is decided (callers that test == REACHED)
