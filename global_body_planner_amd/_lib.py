@@ -52,6 +52,8 @@ EXPORTS = [
     "gbp_tree_create", "gbp_tree_destroy", "gbp_tree_init", "gbp_tree_reserve", "gbp_tree_capacity",
     "gbp_tree_size", "gbp_tree_read", "gbp_tree_append_host", "gbp_tree_load_host",
     "gbp_tree_device_ptrs", "gbp_vertex_map_order", "gbp_vertex_map_rank",
+    "gbp_tree_revalidate_dev", "gbp_tree_prune_dev", "gbp_tree_revalidate_host",
+    "gbp_tree_read_links",
     "gbp_plan_ws_create", "gbp_plan_ws_destroy", "gbp_plan_reset", "gbp_plan_half_dev",
     "gbp_plan_halves_dev", "gbp_plan_star_config", "gbp_plan_stage_timing", "gbp_plan_stage_times",
     "gbp_plan_status_read", "gbp_plan_resolve_host", "gbp_extend_tree_dev",
@@ -65,6 +67,12 @@ class Sampling(ctypes.Structure):
     _fields_ = [("state_flag", ctypes.c_int32), ("state_speed_direction", ctypes.c_int32),
                 ("state_p", ctypes.c_double), ("action_flag", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("action_p", ctypes.c_double)]
+
+
+class PruneStats(ctypes.Structure):
+    """gbp_prune_stats (include/gbp.h): what a prune kept and why the rest went."""
+    _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
+                ("n_edge_invalid", ctypes.c_int64), ("n_inherited", ctypes.c_int64)]
 
 
 def sampling(state_flag=False, state_p=0.05, speed_direction=False, action_flag=False,
@@ -146,11 +154,15 @@ def load(path=None):
         "gbp_tree_capacity": (I, [P, P]),
         "gbp_tree_size": (I, [P, P, P]),
         "gbp_tree_read": (I, [P, I64, I64, P, P, P, P, P]),
+        "gbp_tree_read_links": (I, [P, I64, I64, P, P, P, P]),
         "gbp_tree_append_host": (I, [P, I64, P, P, P, P]),
         "gbp_tree_load_host": (I, [P, I64, P, P, P, P]),
         "gbp_vertex_map_order": (I, [I64, P]),
         "gbp_vertex_map_rank": (I, [I64, I64, P]),
         "gbp_tree_device_ptrs": (I, [P, P, P]),
+        "gbp_tree_revalidate_dev": (I, [P, P, I64, I, I, P, P, P]),
+        "gbp_tree_prune_dev": (I, [P, I64, P, P, P, P]),
+        "gbp_tree_revalidate_host": (I, [P, P, I, I, P, P, P]),
         "gbp_plan_ws_create": (I, [P, I64, P]),
         "gbp_plan_ws_destroy": (I, [P]),
         "gbp_plan_reset": (I, [P, I64, P]),

@@ -47,6 +47,12 @@
 // with decoupled look-back", 2016), so vertices land in exactly the order of
 // the host planner's insertion loop.
 //
+// A tree against a changed terrain (gbp_tree_revalidate_dev, gbp_tree_prune_dev):
+// k_prune_gather writes every edge as an attempt row for the validate kernels,
+// k_prune_seed / k_prune_jump find the vertices whose edges up to the root all
+// hold, k_prune_count / k_prune_scan / k_prune_rank number them in order and
+// k_prune_move_rows / k_prune_move_links move them into fresh arrays.
+//
 // FRAGILE decisions (gbp.h) stop the sequence at the next gate: the kernel
 // that meets one sets status.halt; every later kernel of the group returns at
 // once; the host re-decides the flagged items with glibc
@@ -96,6 +102,9 @@ struct gbp_tree {
   int32_t *prev = nullptr;    // [cap] previous sibling (-1: first child): O(1) removeEdge
   int32_t *bfs = nullptr;     // [2 cap] scratch: the subtree update's two level queues
   int32_t *count = nullptr;   // [1] number of vertices (device resident)
+  // gbp_tree_revalidate_dev's attempt rows (grow-only; kernels do not read these two)
+  void *rv = nullptr;
+  size_t rv_bytes = 0;
 };
 
 // the segment scans k_nn_hreduce lists (a fourth unit of a segment within
@@ -2592,6 +2601,204 @@ __global__ void k_tree_load(gbp_tree t, int64_t n, const double *__restrict__ s,
   *t.count = (int32_t)n;
 }
 
+// ============================================================================
+// pruning a tree against a changed terrain (gbp_tree_revalidate_dev,
+// gbp_tree_prune_dev)
+// ============================================================================
+// Stage A: edge (parent[i] -> i), i in [1, n), as attempt row i - 1 of the
+// validate kernels: s = v[parent[i]], a = a[i].  One 16-B piece per thread, a
+// row's 9 pieces (4 of s, 5 of a) on consecutive lanes.  n must be the tree's
+// device count: otherwise nothing of the tree is read (every row zero) and
+// edge_valid[0] = 0 tells the caller.
+constexpr int PRUNE_PIECES = 9;
+__global__ __launch_bounds__(TB) void k_prune_gather(gbp_tree t, int32_t n, double2 *__restrict__ rs,
+                                                     double2 *__restrict__ ra,
+                                                     uint8_t *__restrict__ edge_valid,
+                                                     uint32_t *__restrict__ flags) {
+  const bool ok = *t.count == n;
+  const double2 *tv = (const double2 *)t.v, *ta = (const double2 *)t.a;
+  const int64_t pieces = (int64_t)(n - 1) * PRUNE_PIECES;
+  const int64_t first = (int64_t)blockIdx.x * TB + threadIdx.x;
+  for (int64_t x = first; x < pieces; x += (int64_t)gridDim.x * TB) {
+    const int64_t row = x / PRUNE_PIECES, i = row + 1;
+    const int k = (int)(x - row * PRUNE_PIECES);
+    double2 val = make_double2(0.0, 0.0);
+    if (k < 4) {
+      const int32_t p = ok ? t.parent[i] : -1;
+      if (p >= 0 && p < n) val = tv[4 * (int64_t)p + k];
+      rs[4 * row + k] = val;
+    } else {
+      if (ok) val = ta[5 * i + (k - 4)];
+      ra[5 * row + (k - 4)] = val;
+    }
+  }
+  if (first == 0) {  // the root is never tested
+    edge_valid[0] = ok ? 1 : 0;
+    flags[0] = 0;
+  }
+}
+
+// Stage B, the keep rule by pointer jumping.  A vertex's word is
+// (ancestor << 1) | dead: after r rounds its 2^r-th ancestor (the root once
+// the path is shorter) and whether one of the 2^r edges up to it failed.  A
+// round reads one buffer and writes the other, so every word read is the
+// previous round's whatever the workgroups' order; ceil(log2 n) rounds reach
+// the root from every vertex (a path has at most n - 1 edges).  A parent
+// outside [0, n) counts as a failed edge below the root.
+__global__ __launch_bounds__(TB) void k_prune_seed(const int32_t *__restrict__ parent,
+                                                   const uint8_t *__restrict__ edge_valid, int32_t n,
+                                                   uint32_t *__restrict__ w) {
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+    uint32_t x = 0;  // the root: its own ancestor, never dead
+    if (i > 0) {
+      const int32_t p = parent[i];
+      x = (p < 0 || p >= n) ? 1u : ((uint32_t)p << 1) | (edge_valid[i] ? 0u : 1u);
+    }
+    w[i] = x;
+  }
+}
+
+__global__ __launch_bounds__(TB) void k_prune_jump(const uint32_t *__restrict__ src,
+                                                   uint32_t *__restrict__ dst, int32_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+    const uint32_t x = src[i], y = src[x >> 1];
+    dst[i] = (y & ~1u) | ((x | y) & 1u);
+  }
+}
+
+// The order-preserving compaction without a wait between workgroups: tile b
+// (CB vertices) counts its kept vertices and its failed edges, one workgroup
+// scans the tiles' counts, then every tile ranks its vertices again from its
+// offset (the same ballots).
+__global__ __launch_bounds__(CB) void k_prune_count(const uint32_t *__restrict__ w,
+                                                    const uint8_t *__restrict__ edge_valid, int32_t n,
+                                                    uint2 *__restrict__ tile) {
+  __shared__ uint32_t sk[CB / WAVE], sb[CB / WAVE];
+  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
+  const bool in = i < n;
+  const bool keep = in && !(w[i] & 1u), bad = in && i > 0 && !edge_valid[i];
+  const unsigned long long mk = __ballot(keep), mb = __ballot(bad);
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    sk[threadIdx.x / WAVE] = (uint32_t)__popcll(mk);
+    sb[threadIdx.x / WAVE] = (uint32_t)__popcll(mb);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t k = 0, b = 0;
+    for (int q = 0; q < CB / WAVE; q++) {
+      k += sk[q];
+      b += sb[q];
+    }
+    tile[blockIdx.x] = make_uint2(k, b);
+  }
+}
+
+// one workgroup: toff[b] = the kept vertices of the tiles before b; the stats
+// record and the tree's new count
+__global__ __launch_bounds__(CB) void k_prune_scan(const uint2 *__restrict__ tile, int64_t ntile,
+                                                   uint32_t *__restrict__ toff, int32_t n,
+                                                   gbp_prune_stats *__restrict__ stats,
+                                                   int32_t *__restrict__ count) {
+  __shared__ uint32_t ws[CB / WAVE], wb[CB / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  uint32_t run = 0, bad = 0;  // the same in every thread
+  for (int64_t base = 0; base < ntile; base += CB) {
+    const int64_t b = base + threadIdx.x;
+    const uint2 c = b < ntile ? tile[b] : make_uint2(0u, 0u);
+    uint32_t incl = c.x, bsum = c.y;  // inclusive scan / sum over the wave
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      const uint32_t up = __shfl_up(incl, d, WAVE);
+      if (lane >= d) incl += up;
+      bsum += __shfl_xor(bsum, d, WAVE);
+    }
+    if (lane == WAVE - 1) ws[wv] = incl;
+    if (lane == 0) wb[wv] = bsum;
+    __syncthreads();
+    uint32_t woff = 0, tot = 0;
+    for (int q = 0; q < CB / WAVE; q++) {
+      if (q < wv) woff += ws[q];
+      tot += ws[q];
+      bad += wb[q];
+    }
+    if (b < ntile) toff[b] = run + woff + incl - c.x;
+    run += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats->n_before = n;
+    stats->n_kept = run;
+    stats->n_edge_invalid = bad;
+    stats->n_inherited = (int64_t)n - run - bad;
+    *count = (int32_t)run;
+  }
+}
+
+__global__ __launch_bounds__(CB) void k_prune_rank(const uint32_t *__restrict__ w, int32_t n,
+                                                   const uint32_t *__restrict__ toff,
+                                                   int32_t *__restrict__ remap) {
+  __shared__ uint32_t sk[CB / WAVE];
+  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const bool keep = i < n && !(w[i] & 1u);
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) sk[wv] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t off = toff[blockIdx.x];
+  for (int q = 0; q < wv; q++) off += sk[q];
+  if (i < n) remap[i] = keep ? (int32_t)(off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) : -1;
+}
+
+// the kept rows of v and a into the fresh arrays, in 16-B pieces like the gather
+__global__ __launch_bounds__(TB) void k_prune_move_rows(gbp_tree o, gbp_tree f, int32_t n,
+                                                        const int32_t *__restrict__ remap) {
+  const double2 *ov = (const double2 *)o.v, *oa = (const double2 *)o.a;
+  double2 *fv = (double2 *)f.v, *fa = (double2 *)f.a;
+  const int64_t pieces = (int64_t)n * PRUNE_PIECES;
+  for (int64_t x = (int64_t)blockIdx.x * TB + threadIdx.x; x < pieces; x += (int64_t)gridDim.x * TB) {
+    const int64_t i = x / PRUNE_PIECES;
+    const int k = (int)(x - i * PRUNE_PIECES);
+    const int64_t j = remap[i];
+    if (j < 0) continue;
+    if (k < 4)
+      fv[4 * j + k] = ov[4 * i + k];
+    else
+      fa[5 * j + (k - 4)] = oa[5 * i + (k - 4)];
+  }
+}
+
+// the next kept vertex of a successor list from c on (c itself included),
+// renumbered; -1 at the list's end.  A list holds at most n vertices: the walk
+// stops there whatever the arrays hold.
+__device__ __forceinline__ int32_t prune_next_kept(int32_t c, const int32_t *__restrict__ link,
+                                                   const int32_t *__restrict__ remap, int32_t n) {
+  for (int32_t steps = 0; c >= 0 && c < n && steps < n; c = link[c], steps++)
+    if (remap[c] >= 0) return remap[c];
+  return -1;
+}
+
+// a kept vertex's g (copied: it is g[parent] + poseDistance already), its
+// parent renumbered, its fp16 row (hm zeroed before this launch), and its
+// places in the successor lists: the old lists with the pruned vertices left
+// out, so each list keeps its order.  Every word written belongs to the
+// vertex's own fresh row.
+__global__ __launch_bounds__(TB) void k_prune_move_links(gbp_tree o, gbp_tree f, int32_t n,
+                                                         const int32_t *__restrict__ remap) {
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+    const int32_t j = remap[i];
+    if (j < 0) continue;
+    const int32_t p = o.parent[i];
+    f.parent[j] = (p >= 0 && p < n) ? remap[p] : -1;
+    f.g[j] = o.g[i];
+    double s[8];
+    copy8(s, o.v + 8 * i);
+    nn_put_hrow(f.vh, f.hm, j, s, false);
+    f.child[j] = prune_next_kept(o.child[i], o.sibling, remap, n);
+    f.sibling[j] = prune_next_kept(o.sibling[i], o.sibling, remap, n);
+    f.prev[j] = prune_next_kept(o.prev[i], o.prev, remap, n);
+  }
+}
+
 __global__ void k_plan_reset(gbp_plan_status *st, int64_t ext_counter, gbp_plan_la *la) {
   *la = gbp_plan_la{};  // no drawn-ahead targets, empty snapshots
   gbp_plan_status z;
@@ -3278,6 +3485,7 @@ int gbp_tree_destroy(gbp_tree *t) {
   tree_free_arrays(t);
   if (t->hm) (void)hipFree(t->hm);
   if (t->count) (void)hipFree(t->count);
+  if (t->rv) (void)hipFree(t->rv);
   delete t;
   return GBP_OK;
 }
@@ -3355,6 +3563,22 @@ int gbp_tree_read(gbp_tree *t, int64_t first, int64_t n, double *states, double 
   return GBP_OK;
 }
 
+int gbp_tree_read_links(gbp_tree *t, int64_t first, int64_t n, int32_t *child, int32_t *sibling,
+                        int32_t *prev, gbp_stream stream) {
+  if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
+  if (first < 0 || n < 0 || first + n > t->cap) return GBP_E_INVALID_ARG;
+  if (n == 0) return GBP_OK;
+  DeviceGuard gd(t->device);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = GBP_OK;
+  if (!rc && child) rc = d2h(child, t->child + first, n, s);
+  if (!rc && sibling) rc = d2h(sibling, t->sibling + first, n, s);
+  if (!rc && prev) rc = d2h(prev, t->prev + first, n, s);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  return GBP_OK;
+}
+
 int gbp_tree_append_host(gbp_tree *t, int64_t n, const double *states, const double *actions,
                          const int32_t *parents, gbp_stream stream) {
   if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
@@ -3395,6 +3619,159 @@ int gbp_tree_device_ptrs(gbp_tree *t, double **states, int32_t **count) {
   if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
   if (states) *states = t->v;
   if (count) *count = t->count;
+  return GBP_OK;
+}
+
+// ---- pruning against a changed terrain ---------------------------
+namespace {
+// stage A's attempt rows in the tree's own grow-only buffer (the call only
+// enqueues: nothing of it may be freed when it returns)
+int prune_rows(gbp_tree *tree, int64_t n, double *&rs, double *&ra) {
+  auto carve = [&](Stage &S) { S.take(rs, 8 * (n - 1)); S.take(ra, 10 * (n - 1)); };
+  const int rc = ensure_ws(&tree->rv, &tree->rv_bytes, stage_bytes_of(carve));
+  return rc ? rc : stage_carve(tree->rv, tree->rv_bytes, carve);
+}
+int prune_args(const gbp_tree *tree, int64_t n, bool arrays) {
+  if (!tree_ok(tree)) return GBP_E_BAD_HANDLE;
+  if (n < 1 || !arrays) return GBP_E_INVALID_ARG;
+  return n > tree->cap ? GBP_E_SHAPE : GBP_OK;
+}
+}  // namespace
+
+int gbp_tree_revalidate_dev(gbp_terrain *t, gbp_tree *tree, int64_t n, int direction, int adaptive,
+                            uint8_t *edge_valid, uint32_t *flags, gbp_stream stream) {
+  if (!t) return GBP_E_BAD_HANDLE;
+  int rc = prune_args(tree, n, edge_valid && flags);
+  if (rc) return rc;
+  if (direction != GBP_FORWARD && direction != GBP_REVERSE) return GBP_E_INVALID_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
+  if (!t->d_z) return GBP_E_BAD_HANDLE;
+  if (t->device != tree->device) return GBP_E_INVALID_ARG;
+  DeviceGuard g(tree->device);
+  hipStream_t s = (hipStream_t)stream;
+  double *rs = nullptr, *ra = nullptr;
+  if (n > 1 && (rc = prune_rows(tree, n, rs, ra))) return rc;
+  hipLaunchKernelGGL(k_prune_gather, dim3(grid_for((n - 1) * PRUNE_PIECES, TB, t->num_cus * 8)),
+                     dim3(TB), 0, s, *tree, (int32_t)n, (double2 *)rs, (double2 *)ra, edge_valid, flags);
+  HIPCHK(hipGetLastError());
+  if (n == 1) return GBP_OK;
+  // vertex i's decision is row i - 1's: straight into edge_valid[i] / flags[i]
+  return gbp_validate_pairs_dev(t, n - 1, rs, ra, nullptr, direction, adaptive, edge_valid + 1, nullptr,
+                                nullptr, flags + 1, nullptr, stream);
+}
+
+int gbp_tree_prune_dev(gbp_tree *tree, int64_t n, const uint8_t *edge_valid, int32_t *remap,
+                       gbp_prune_stats *stats, gbp_stream stream) {
+  int rc = prune_args(tree, n, edge_valid && remap && stats);
+  if (rc) return rc;
+  int64_t have = 0;
+  if ((rc = gbp_tree_size(tree, &have, stream))) return rc;  // synchronises
+  if (have != n) return GBP_E_SHAPE;
+  DeviceGuard g(tree->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t ntile = (n + CB - 1) / CB;
+  DevBuf buf;
+  uint32_t *w[2], *toff;
+  uint2 *tile;
+  rc = stage_buf(buf, [&](Stage &S) {
+    S.take(w[0], n); S.take(w[1], n); S.take(tile, ntile); S.take(toff, ntile);
+  });
+  if (rc) return rc;
+  // the survivors get arrays, a count and search bounds of their own: until
+  // the swap below the tree is untouched, so a failed call leaves it as it was
+  gbp_tree fresh = *tree;
+  if ((rc = tree_alloc(&fresh, tree->cap))) return rc;
+  fresh.count = nullptr;
+  fresh.hm = nullptr;
+  auto drop_fresh = [&]() {
+    tree_free_arrays(&fresh);
+    if (fresh.count) (void)hipFree(fresh.count);
+    if (fresh.hm) (void)hipFree(fresh.hm);
+  };
+  if (hipMalloc(&fresh.count, 4) != hipSuccess || hipMalloc(&fresh.hm, 64) != hipSuccess) {
+    drop_fresh();
+    return GBP_E_ALLOC;
+  }
+  const unsigned gv = grid_for(n, TB, 2048);
+  hipLaunchKernelGGL(k_prune_seed, dim3(gv), dim3(TB), 0, s, tree->parent, edge_valid, (int32_t)n, w[0]);
+  int cur = 0;  // ceil(log2 n) rounds, back to back
+  for (int64_t reach = 1; reach < n; reach <<= 1, cur ^= 1)
+    hipLaunchKernelGGL(k_prune_jump, dim3(gv), dim3(TB), 0, s, w[cur], w[cur ^ 1], (int32_t)n);
+  hipLaunchKernelGGL(k_prune_count, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], edge_valid, (int32_t)n,
+                     tile);
+  hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(CB), 0, s, tile, ntile, toff, (int32_t)n, stats,
+                     fresh.count);
+  hipLaunchKernelGGL(k_prune_rank, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], (int32_t)n, toff, remap);
+  bool ok = hipGetLastError() == hipSuccess && hipMemsetAsync(fresh.hm, 0, 64, s) == hipSuccess;
+  if (ok) {
+    hipLaunchKernelGGL(k_prune_move_rows, dim3(grid_for(n * PRUNE_PIECES, TB, 2048)), dim3(TB), 0, s,
+                       *tree, fresh, (int32_t)n, remap);
+    hipLaunchKernelGGL(k_prune_move_links, dim3(gv), dim3(TB), 0, s, *tree, fresh, (int32_t)n, remap);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) {
+    (void)hipDeviceSynchronize();
+    drop_fresh();
+    return GBP_E_HIP;
+  }
+  tree_free_arrays(tree);
+  (void)hipFree(tree->count);
+  (void)hipFree(tree->hm);
+  *tree = fresh;
+  return GBP_OK;
+}
+
+int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
+                             int32_t *remap, gbp_prune_stats *stats, int64_t *n_resolved) {
+  if (n_resolved) *n_resolved = 0;
+  if (!t || !tree_ok(tree)) return GBP_E_BAD_HANDLE;
+  if (!stats || (direction != GBP_FORWARD && direction != GBP_REVERSE)) return GBP_E_INVALID_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
+  if (!t->d_z) return GBP_E_BAD_HANDLE;
+  DeviceGuard g(tree->device);
+  hipStream_t s = t->host_stream;
+  int64_t n = 0;
+  int rc = gbp_tree_size(tree, &n, s);
+  if (rc) return rc;
+  // edge_valid and flags back to back: one read-back
+  const size_t fl_at = ((size_t)n + 255) & ~(size_t)255;
+  const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
+  DevBuf buf;
+  uint8_t *dev;
+  int32_t *dmap;
+  gbp_prune_stats *dst;
+  rc = stage_buf(buf, [&](Stage &S) { S.take(dev, dec_bytes); S.take(dmap, n); S.take(dst, 1); });
+  if (rc) return rc;
+  uint32_t *dfl = (uint32_t *)(dev + fl_at);
+  if ((rc = gbp_tree_revalidate_dev(t, tree, n, direction, adaptive, dev, dfl, s))) return rc;
+  std::vector<uint8_t> dec(dec_bytes);
+  if ((rc = d2h(dec.data(), dev, dec_bytes, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  uint8_t *ev = dec.data();
+  uint32_t *fl = (uint32_t *)(dec.data() + fl_at);
+  bool fragile = false;
+  for (int64_t i = 1; i < n && !fragile; i++) fragile = (fl[i] & GBP_F_FRAGILE) != 0;
+  if (fragile) {
+    // the FRAGILE edges again with glibc, from the rows stage A gathered: the
+    // rows in one copy, the decisions back in one
+    double *rs = nullptr, *ra = nullptr;
+    if ((rc = prune_rows(tree, n, rs, ra))) return rc;  // (the buffer stage A filled)
+    std::vector<double> hs(8 * (n - 1)), ha(10 * (n - 1));
+    if ((rc = d2h(hs.data(), rs, 8 * (n - 1), s))) return rc;
+    if ((rc = d2h(ha.data(), ra, 10 * (n - 1), s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    rc = gbp_resolve_fragile_host(t, n - 1, hs.data(), ha.data(), nullptr, direction, adaptive, ev + 1,
+                                  nullptr, nullptr, fl + 1, nullptr, n_resolved);
+    if (!rc) rc = h2d(dev, ev, n, s);
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(s));  // dec leaves scope only after the copy
+  }
+  if ((rc = gbp_tree_prune_dev(tree, n, dev, dmap, dst, s))) return rc;
+  if (remap && (rc = d2h(remap, dmap, n, s))) return rc;
+  if ((rc = d2h(stats, dst, 1, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
   return GBP_OK;
 }
 

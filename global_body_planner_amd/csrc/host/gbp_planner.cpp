@@ -7,6 +7,7 @@
 // planning_utils is gbp_planning_math.cpp, the path join gbp_tree_path.cpp.
 #include "gbp_planner.h"
 #include "gbp_tree_path.h"
+#include "gbp_tree_prune.h"
 #include "../gbp_um_order.h"
 
 #include <algorithm>
@@ -1311,6 +1312,52 @@ static void dump_trees(const PlannerClass &Ta, const PlannerClass &Tb, TreeDump 
       d->parent[k][i] = t[k]->getPredecessor(i);
       d->g[k][i] = t[k]->getGValue(i);
     }
+  }
+}
+
+void RRTConnectClass::revalidateTrees(FastTerrainMap &terrain, TreeDump &trees, PruneStats stats[2],
+                                      std::vector<int32_t> remap[2]) {
+  struct Tree {  // the device tree of one call
+    gbp_tree *t = nullptr;
+    ~Tree() {
+      if (t) gbp_tree_destroy(t);
+    }
+  };
+  // both trees are decided before either host copy changes: a call that
+  // throws leaves `trees`, `stats` and `remap` as they were
+  std::vector<int32_t> map[2];
+  PruneStats done[2];
+  for (int k = 0; k < 2; k++) {
+    const int64_t n = (int64_t)trees.v[k].size();
+    if (n < 1 || (int64_t)trees.a[k].size() != n || (int64_t)trees.parent[k].size() != n ||
+        (int64_t)trees.g[k].size() != n)
+      throw EngineError(GBP_E_INVALID_ARG, "revalidateTrees: tree arrays");
+    Tree T;
+    chk(gbp_tree_create(terrain.device(), n, &T.t), "revalidateTrees: tree");
+    chk(gbp_tree_load_host(T.t, n, trees.v[k][0].data(), trees.a[k][0].data(), trees.parent[k].data(),
+                           nullptr),
+        "revalidateTrees: tree load");
+    map[k].resize(n);
+    gbp_prune_stats ps{};
+    chk(gbp_tree_revalidate_host(terrain.handle(), T.t, k == 0 ? FORWARD : REVERSE,
+                                 state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0,
+                                 map[k].data(), &ps, &done[k].fragile_resolved),
+        "revalidateTrees");
+    done[k].n_before = ps.n_before;
+    done[k].n_kept = ps.n_kept;
+    done[k].n_edge_invalid = ps.n_edge_invalid;
+    done[k].n_inherited = ps.n_inherited;
+  }
+  // the survivors from the host copies: the device moved the same rows (g is
+  // copied there too, not derived again)
+  TreeDump kept = trees;
+  for (int k = 0; k < 2; k++)
+    if (!applyPruneRemap(map[k], kept, k) || (int64_t)kept.v[k].size() != done[k].n_kept)
+      throw EngineError(GBP_E_INVALID_ARG, "revalidateTrees: remap");
+  trees = std::move(kept);
+  for (int k = 0; k < 2; k++) {
+    stats[k] = done[k];
+    if (remap) remap[k] = std::move(map[k]);
   }
 }
 

@@ -1,0 +1,46 @@
+// gbp_tree_prune.cpp — see gbp_tree_prune.h
+#include "gbp_tree_prune.h"
+
+namespace gbp_amd {
+
+int64_t applyPruneRemap(const int32_t *remap, int64_t n, State *v, Action *a, int32_t *parent,
+                        double *g) {
+  if (n < 1 || !remap || !v || !a || !parent || remap[0] != 0 || parent[0] != -1) return -1;
+  // the whole map is checked before the first row moves
+  int64_t kept = 0;
+  for (int64_t i = 0; i < n; i++) {
+    if (remap[i] < 0) continue;
+    if (remap[i] != kept) return -1;
+    if (i > 0 && (parent[i] < 0 || parent[i] >= n || remap[parent[i]] < 0)) return -1;
+    kept++;
+  }
+  // a row moves down or stays (remap[i] <= i), so no unread row is overwritten;
+  // a parent is renumbered from remap, never from a moved row
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t j = remap[i];
+    if (j < 0) continue;
+    const int32_t p = parent[i];
+    v[j] = v[i];
+    a[j] = a[i];
+    if (g) g[j] = g[i];
+    parent[j] = p >= 0 ? remap[p] : -1;
+  }
+  return kept;
+}
+
+bool applyPruneRemap(const std::vector<int32_t> &remap, TreeDump &trees, int k) {
+  const size_t n = remap.size();
+  if (k < 0 || k > 1 || trees.v[k].size() != n || trees.a[k].size() != n ||
+      trees.parent[k].size() != n || trees.g[k].size() != n)
+    return false;
+  const int64_t kept = applyPruneRemap(remap.data(), (int64_t)n, trees.v[k].data(), trees.a[k].data(),
+                                       trees.parent[k].data(), trees.g[k].data());
+  if (kept < 0) return false;
+  trees.v[k].resize(kept);
+  trees.a[k].resize(kept);
+  trees.parent[k].resize(kept);
+  trees.g[k].resize(kept);
+  return true;
+}
+
+}  // namespace gbp_amd

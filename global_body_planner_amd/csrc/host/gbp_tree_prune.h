@@ -1,0 +1,24 @@
+// gbp_tree_prune.h — a prune's remap (gbp_tree_prune_dev, include/gbp.h)
+// applied to the host copy of a tree.  Pure host code with no engine call.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "gbp_planner.h"
+
+namespace gbp_amd {
+
+// remap[n]: a vertex's new index or -1, as the device prune returns it — the
+// kept vertices numbered 0, 1, ... in their order, the root kept as 0, a kept
+// vertex's parent kept.  Moves the kept rows of v / a / parent / g (each of n
+// rows; g may be null) to the front in place, parent as remap[parent], and
+// returns how many there are; -1, with nothing changed, when remap is no such
+// map for these parents.
+int64_t applyPruneRemap(const int32_t *remap, int64_t n, State *v, Action *a, int32_t *parent,
+                        double *g);
+
+// tree k of a TreeDump (its four vectors shortened to the survivors)
+bool applyPruneRemap(const std::vector<int32_t> &remap, TreeDump &trees, int k);
+
+}  // namespace gbp_amd

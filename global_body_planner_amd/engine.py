@@ -414,6 +414,38 @@ class DeviceTree:
         check(self._lib.gbp_tree_append_host(self._h, s.shape[0], _np_ptr(s), _np_ptr(a), _np_ptr(p),
                                              None), "tree_append")
 
+    def load(self, states, actions, parents):
+        """gbp_tree_load_host: replaces the tree with the given vertices (vertex 0
+        the root, parents[0] = -1; parents may follow their children, as RRT*'s
+        rewiring leaves them); g is derived on the device from the root down."""
+        s = np.ascontiguousarray(states, np.float64).reshape(-1, 8)
+        a = np.ascontiguousarray(actions, np.float64).reshape(-1, 10)
+        p = np.ascontiguousarray(parents, np.int32).reshape(-1)
+        if not s.shape[0] == a.shape[0] == p.shape[0]:
+            raise ValueError("states, actions and parents differ in length")
+        check(self._lib.gbp_tree_load_host(self._h, s.shape[0], _np_ptr(s), _np_ptr(a), _np_ptr(p),
+                                           None), "tree_load")
+
+    def revalidate(self, terrain, direction, adaptive=False):
+        """gbp_tree_revalidate_host: prunes the tree against `terrain` (an
+        engine.Terrain holding the changed map).  A vertex stays when the pair
+        check of (v[parent], action, direction) holds on that terrain for every
+        edge between it and the root; the root is never tested.  Returns
+        (remap, stats): remap [n before] int32, a vertex's new index or -1;
+        stats a dict of n_before, n_kept, n_edge_invalid (pruned vertices whose
+        own edge failed), n_inherited (pruned through an ancestor only) and
+        n_resolved (FRAGILE edges re-decided on the host with glibc)."""
+        remap = np.empty(len(self), np.int32)
+        st = L.PruneStats()
+        k = ctypes.c_int64(0)
+        check(self._lib.gbp_tree_revalidate_host(terrain._h, self._h, int(direction),
+                                                 int(bool(adaptive)), _np_ptr(remap),
+                                                 ctypes.byref(st), ctypes.byref(k)),
+              "tree_revalidate")
+        stats = {name: getattr(st, name) for name, _ in L.PruneStats._fields_}
+        stats["n_resolved"] = k.value
+        return remap, stats
+
     def read(self):
         """(states [n][8], actions [n][10], parents [n], g [n]) numpy."""
         n = len(self)
@@ -422,6 +454,16 @@ class DeviceTree:
         check(self._lib.gbp_tree_read(self._h, 0, n, _np_ptr(s), _np_ptr(a), _np_ptr(p), _np_ptr(g),
                                       None), "tree_read")
         return s, a, p, g
+
+
+    def read_links(self):
+        """(child [n], sibling [n], prev [n]) numpy int32: the successor lists
+        (gbp_tree_read_links) — first child, next and previous sibling, -1 none."""
+        n = len(self)
+        c, s, p = (np.empty(n, np.int32) for _ in range(3))
+        check(self._lib.gbp_tree_read_links(self._h, 0, n, _np_ptr(c), _np_ptr(s), _np_ptr(p), None),
+              "tree_read_links")
+        return c, s, p
 
 
 class PlanStatus(ctypes.Structure):

@@ -297,6 +297,41 @@ def shortcut_paths(terrain_or_data, paths, actions, adaptive=False, cost_add_yaw
             "path_cost": co[:n_paths].copy(), "n_resolved": nres.value}
 
 
+def revalidate_trees(data, trees, adaptive=False, device=0):
+    """The trees of an earlier search against a changed map: what of them a
+    new search on `data` (terrain_data.TerrainData, or an engine.Terrain) may
+    start from.
+
+    trees: (a, b) dicts of v [n][8], act [n][10], parent [n] — what
+    plan_rrt_connect(..., trees=True) returns and init_trees= takes; tree a
+    was grown FORWARD, tree b REVERSE.  Each is loaded into HBM and pruned
+    there (engine.DeviceTree.revalidate): a vertex stays when every edge
+    between it and the root still passes its pair check on the new map.  The
+    roots are kept untested.  Returns (pruned_trees, remaps, stats): the
+    survivors as (a, b) dicts of v, act, parent, g; per tree the int32 map from
+    an old index to the new one (-1: pruned), for callers that carry vertex
+    indices of their own across the prune; per tree the stats dict."""
+    from . import engine
+    own = not isinstance(data, engine.Terrain)
+    T = engine.Terrain.from_data(data, device=device) if own else data
+    pruned, remaps, stats = [], [], []
+    try:
+        for direction, t in zip((_lib.FORWARD, _lib.REVERSE), trees):
+            v = np.ascontiguousarray(t["v"], np.float64).reshape(-1, 8)
+            tree = engine.DeviceTree(v[0], device=T.device, capacity=max(v.shape[0], 1))
+            tree.load(v, t["act"], t["parent"])
+            remap, st = tree.revalidate(T, direction, adaptive=adaptive)
+            s, a, p, g = tree.read()
+            pruned.append(dict(v=s, act=a, parent=p, g=g))
+            remaps.append(remap)
+            stats.append(st)
+            del tree
+    finally:
+        if own:
+            T.close()
+    return tuple(pruned), tuple(remaps), tuple(stats)
+
+
 def attempt_connect(terrain, s_existing, s, direction, t_s=None, adaptive=False, s_new=None,
                     a_new=None):
     """RRTConnectClass::attemptConnect (rrt_connect.cpp:20-91) for n pairs on an

@@ -432,6 +432,12 @@ int gbp_tree_size(gbp_tree *tree, int64_t *count, gbp_stream stream);  /* synchr
 /* host copies of vertices [first, first + n); any output may be NULL (synchronous) */
 int gbp_tree_read(gbp_tree *tree, int64_t first, int64_t n, double *states, double *actions,
                   int32_t *parents, double *g, gbp_stream stream);
+/* the successor lists (graph_class.cpp:28-58 successors_) of vertices [first,
+ * first + n) as the tree keeps them: child = a vertex's first child, sibling =
+ * the next child of its parent, prev = the one before it, -1 = none (the order
+ * within a list carries no meaning); any output may be NULL (synchronous) */
+int gbp_tree_read_links(gbp_tree *tree, int64_t first, int64_t n, int32_t *child,
+                        int32_t *sibling, int32_t *prev, gbp_stream stream);
 /* appends n vertices (addVertex + addEdge + addAction) in order; g computed on
  * the device; parents may name vertices appended earlier in the same call */
 int gbp_tree_append_host(gbp_tree *tree, int64_t n, const double *states, const double *actions,
@@ -454,6 +460,58 @@ int gbp_tree_nearest_dev(gbp_plan_ws *ws, gbp_tree *tree, int64_t n, const doubl
  * vertices are written through init / append only, which also keep the fp16
  * rows and magnitude bounds the matrix-core search relies on */
 int gbp_tree_device_ptrs(gbp_tree *tree, double **states, int32_t **count);
+
+/* ---- a tree against a changed terrain ---------------------------------------
+ * The map reaches the reference node through a callback
+ * (global_body_planner.cpp:37-44) and the node plans on it again; a tree grown
+ * on the map before keeps the vertices that are still reachable on the new
+ * one.  Edge (parent[i] -> i) of a tree grown in `direction` was inserted
+ * because the pair check of (v[parent[i]], a[i], direction) was valid (extend,
+ * rrt.cpp:77-102; the connect's last level, rrt_connect.cpp:20-91; the RRT*
+ * rewire, rrt_star_connect.cpp:55-62): the edge is valid on terrain t when
+ * that check is.  A vertex is kept when every edge between it and the root
+ * is.  The root is never tested (a goal root may be FLIGHT-valid only:
+ * callers test roots with gbp_valid_states_*), and v[i] is not compared with
+ * the check's s_new: only the decision is used. */
+typedef struct {
+  int64_t n_before;        /* vertices of the tree before the prune            */
+  int64_t n_kept;          /* ... and after it                                 */
+  int64_t n_edge_invalid;  /* pruned vertices whose own edge failed            */
+  int64_t n_inherited;     /* pruned only because an ancestor was              */
+} gbp_prune_stats;
+/* Stage A: the edges' decisions on terrain t.  n = the tree's size as the
+ * caller knows it (gbp_tree_size); device edge_valid[n], flags[n]:
+ * edge_valid[i] = the returned bool and flags[i] = the GBP_F_* word of vertex
+ * i's edge, edge_valid[0] = 1, flags[0] = 0.  Enqueue-only on `stream`, with
+ * one exception: the rows live in one buffer the tree owns, and a call that
+ * finds it too small (the first, or one after the tree grew) frees and
+ * allocates it, which synchronises the device.  Because of that buffer, two
+ * calls on the same tree must not be in flight at once.  A FRAGILE edge is
+ * left to the caller to re-decide.  GBP_E_SHAPE when n exceeds the tree's
+ * capacity; when n is not the device's count the kernels read nothing of the
+ * tree and report it as edge_valid[0] = 0 (gbp_tree_prune_dev then returns
+ * GBP_E_SHAPE). */
+int gbp_tree_revalidate_dev(gbp_terrain *t, gbp_tree *tree, int64_t n, int direction, int adaptive,
+                            uint8_t *edge_valid, uint32_t *flags, gbp_stream stream);
+/* Stage B: keeps the vertices whose edges up to the root all have
+ * edge_valid = 1 (device edge_valid[n], [0] ignored), in their order: device
+ * remap[n] = a vertex's new index or -1, the kept rows of v / a / g moved,
+ * parent = remap[parent], the fp16 search rows and successor lists rebuilt,
+ * the count set; device stats[1].  The rows go into fresh arrays that replace
+ * the tree's, with a count and search bounds of their own (the capacity
+ * stays; pointers from gbp_tree_device_ptrs are stale afterwards, as after a
+ * reserve that grew the tree).  Synchronises the stream (before, to compare n
+ * with the device's count: GBP_E_SHAPE when they differ; and after, to free
+ * the old arrays).  The swap is the last step: a call that returns an error
+ * leaves the tree as it was (remap and stats may have been written). */
+int gbp_tree_prune_dev(gbp_tree *tree, int64_t n, const uint8_t *edge_valid, int32_t *remap,
+                       gbp_prune_stats *stats, gbp_stream stream);
+/* Both stages, synchronous, on the terrain's own stream: stage A, one
+ * read-back of the flags, the FRAGILE edges re-decided with glibc
+ * (gbp_resolve_fragile_host: GBP_F_RESOLVED, *n_resolved, may be NULL), stage
+ * B.  Host remap[size of the tree before] (may be NULL) and stats[1]. */
+int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
+                             int32_t *remap, gbp_prune_stats *stats, int64_t *n_resolved);
 
 /* ---- the device planner loop (RRTConnectClass::runRRTConnect,
  *      rrt_connect.cpp:230-314, batch-synchronous) ---------------------------

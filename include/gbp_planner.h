@@ -474,6 +474,16 @@ struct BatchStats {
   int64_t stage_halves = 0;
 };
 
+// What RRTConnectClass::revalidateTrees did to one tree (gbp_prune_stats,
+// include/gbp.h, and the FRAGILE edges re-decided on the host with glibc).
+struct PruneStats {
+  int64_t n_before = 0;        // vertices before the prune
+  int64_t n_kept = 0;          // ... and after it
+  int64_t n_edge_invalid = 0;  // pruned vertices whose own edge failed on the new map
+  int64_t n_inherited = 0;     // pruned only because an ancestor was
+  int64_t fragile_resolved = 0;
+};
+
 class RRTConnectClass : public RRTClass {
  public:
   // rrt_connect.cpp:20-84 (recursive; the pair checks run on the engine)
@@ -541,6 +551,21 @@ class RRTConnectClass : public RRTClass {
   // path_cost_.  Off by default.
   void set_post_process_device(bool on) { post_process_device_ = on; }
   bool post_process_device() const { return post_process_device_; }
+
+  // The map changed (the node's terrainMapCallback, global_body_planner.cpp:37-44,
+  // loads a new one): what of an earlier search's trees (BatchStats::dump; Ta
+  // grown FORWARD, Tb REVERSE) a search on `terrain` may start from.  Each tree
+  // is loaded into HBM and pruned there (gbp_tree_revalidate_host, with this
+  // object's adaptive-step flag): a vertex stays when every edge between it and
+  // the root still passes its pair check on `terrain`; the roots are kept
+  // untested.  `trees` is left holding the survivors, ready for
+  // BatchStats::warm_*; remap (optional, one vector per tree) receives each old
+  // vertex's new index or -1, for callers that carry vertex indices of their
+  // own (RRT*'s kept connections) across the prune.  Both trees are decided
+  // before either is changed: a call that throws (EngineError) leaves trees,
+  // stats and remap as they were.
+  void revalidateTrees(FastTerrainMap &terrain, TreeDump &trees, PruneStats stats[2],
+                       std::vector<int32_t> remap[2] = nullptr);
 
   // attemptConnect for many independent pairs (lock-step rounds, one engine
   // launch per recursion depth); s_new / a_new are in/out per pair
