@@ -44,10 +44,34 @@ constexpr int WAVE = 64;
 // CM == 1: the coordinate vectors are staged in LDS (bracket fix-up and the
 // bilinear x1/x2/y1/y2 then never touch global memory); CM == 2 computes
 // them (gbp_device.h coord)
+// The copy moves 16 B per lane and trip: pair p is the doubles 2p, 2p + 1 of
+// x followed by y (the LDS side is always 16-B aligned; the vectors are 16-B
+// aligned allocations, so the y side is too unless nx is odd).  An odd nx
+// puts x's last double and y's first into one pair; an odd nx + ny pads the
+// last pair with 0 (stage_bytes rounds up to it).
 template <class ZT>
 __device__ __forceinline__ TerrainView<ZT> stage_coords(const TerrainView<ZT> &T0, double *smem) {
-  for (int i = threadIdx.x; i < T0.nx; i += blockDim.x) smem[i] = T0.x[i];
-  for (int i = threadIdx.x; i < T0.ny; i += blockDim.x) smem[T0.nx + i] = T0.y[i];
+  const int nx = T0.nx, nxy = T0.nx + T0.ny;
+  const bool y16 = (nx & 1) == 0;
+  for (int p = threadIdx.x; 2 * p < nxy; p += blockDim.x) {
+    const int e = 2 * p;
+    double2 v;
+    if (e + 1 < nx) {
+      v = *(const double2 *)(T0.x + e);
+    } else if (e >= nx) {
+      const double *q = T0.y + (e - nx);
+      if (y16 && e + 1 < nxy) {
+        v = *(const double2 *)q;
+      } else {
+        v.x = q[0];
+        v.y = e + 1 < nxy ? q[1] : 0.0;
+      }
+    } else {  // e == nx - 1, nx odd: the join of x and y
+      v.x = T0.x[e];
+      v.y = T0.y[0];
+    }
+    ((double2 *)smem)[p] = v;
+  }
   TerrainView<ZT> T = T0;
   T.x = smem;
   T.y = smem + T0.nx;
@@ -178,7 +202,8 @@ constexpr int SN_RING = 2 * 64;  // entries per wave: < 64 left + up to 64 queue
 // (diagnostic build, -DGBP_LOOP_PROF: cycles per phase of the persistent loop,
 // per wave, read by gbp_loop_prof_read; tools/loop_prof.py)
 #ifdef GBP_LOOP_PROF
-__device__ unsigned long long gbp_loop_prof[8192 * 12];
+constexpr int LP_N = 14;  // values per wave
+__device__ unsigned long long gbp_loop_prof[8192 * LP_N];
 #define LP_T(v) const unsigned long long v = __builtin_readcyclecounter()
 #define LP_ADD(k, a, b) lp[k] += (b) - (a)
 #else
@@ -234,6 +259,9 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     const uint8_t *__restrict__ dir, int dir_all, uint8_t *__restrict__ valid,
     double *__restrict__ s_new, double *__restrict__ t_new, uint32_t *__restrict__ flags,
     uint32_t *__restrict__ counts, const int *__restrict__ n_dev, int helpers, int xcd_map, int pf) {
+#ifdef GBP_LOOP_PROF
+  const unsigned long long lp_entry = __builtin_amdgcn_s_memrealtime();
+#endif
   if (n_dev) n = *n_dev;  // batch size produced on the device (planner loop)
   const int lane = threadIdx.x & (WAVE - 1);
   const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -272,6 +300,8 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   };
 #ifdef GBP_REFILL_WINDOW
   // the wave's first rows, fetched (cold) ahead of the coordinate staging
+  // (without the window too this measured slower than filling in the loop's
+  // first refill: DESIGN section 5.1, profiles/wg_handover_ab.txt)
   const unsigned int take0 = min(end - cur, (unsigned int)WAVE);
   double row0[18];
   int dir0 = dir_all;
@@ -323,7 +353,8 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   cur += take0;
 #endif
 #ifdef GBP_LOOP_PROF
-  unsigned long long lp[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long lp[LP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  lp[12] = lp_entry;  // the wave's entry; lp[13]: its first sample (staging and first fill done)
   lp[8] = __builtin_amdgcn_s_memrealtime();
   LP_T(lp_start);
 #endif
@@ -384,6 +415,9 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     if (!act) break;
     LP_T(t1);
     LP_ADD(0, t0, t1);
+#ifdef GBP_LOOP_PROF
+    if (!lp[7]) lp[13] = __builtin_amdgcn_s_memrealtime();
+#endif
     const bool owner = L.stage != ST_IDLE;
     asm volatile("" ::: "memory");  // re-read attempt rows per step (no long live ranges)
     // ---- the sample each lane evaluates this step --------------------------
@@ -518,7 +552,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   }
   const unsigned int gw = blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
   if (lane == 0 && gw < 8192)
-    for (int k = 0; k < 12; k++) gbp_loop_prof[12 * gw + k] = lp[k];
+    for (int k = 0; k < LP_N; k++) gbp_loop_prof[LP_N * gw + k] = lp[k];
 #endif
 }
 
@@ -914,14 +948,30 @@ int coord_mode(const gbp_terrain *t, bool lds_ok) {
   return (t->opt_affine && t->affine) ? 2 : 0;
 }
 
+// Workgroup size of the validate launches: the one place it is chosen (the
+// coordinate mode, the window, the LDS request and the grid all size from it).
+// GBP_OPT_BLOCK, once set, is used as given.  Unset (0), the persistent kernel
+// runs 128 lanes where opt_waves * 2 such workgroups, each with its staged
+// coordinate vectors, fit a CU's 160 KB: the same waves per CU and the same
+// slices as with 256 lanes, measured 1.7-2.4 % faster on the overlapped
+// headline and 8 % on config 2.  Otherwise 256 lanes, as
+// do the direct kernel and the planner loop's launches (n_dev).
+int validate_block(const gbp_terrain *t, bool n_dev) {
+  if (t->opt_block) return (int)t->opt_block;
+  const size_t wg = stage_bytes(t->nx, t->ny) + rows_bytes(128, 0);
+  if (!n_dev && (size_t)t->opt_waves * 2 * wg <= 160 * 1024) return 128;
+  return 256;
+}
+
 // the validate kernels' coordinate mode: LDS only if the vectors fit next to
-// the attempt rows with room for the W workgroups of 256 lanes that share a CU
-// (160 KB per CU; the direct kernel has no rows)
-int validate_coord_mode(const gbp_terrain *t, bool direct) {
+// the attempt rows with room for the workgroups that share a CU (opt_waves of
+// 256 lanes, twice as many of 128; 160 KB per CU; the direct kernel has no rows)
+int validate_coord_mode(const gbp_terrain *t, bool direct, bool n_dev = false) {
   // the attempt rows and s_new rings are the persistent kernel's alone
   // (launch_validate_w allocates neither for the direct kernel)
-  const size_t rows = direct ? 0 : rows_bytes((int)t->opt_block, 0);
-  const size_t per_cu = std::max<int64_t>(1, t->opt_waves * 256 / t->opt_block) *
+  const int block = validate_block(t, n_dev);
+  const size_t rows = direct ? 0 : rows_bytes(block, 0);
+  const size_t per_cu = std::max<int64_t>(1, t->opt_waves * 256 / block) *
                         (stage_bytes(t->nx, t->ny) + rows);
   const bool lds_ok = t->opt_lds_coords && stage_bytes(t->nx, t->ny) + rows <= t->lds_max &&
                       (direct || per_cu <= 160 * 1024);
@@ -937,11 +987,11 @@ int validate_coord_mode(const gbp_terrain *t, bool direct) {
 // a workgroup's limit and among the workgroups that share a CU's 160 KB; 0
 // (every refill loads its rows itself) when nothing fits.  The coordinate mode
 // is chosen first (validate_coord_mode) and never gives way to the window.
-int refill_window(const gbp_terrain *t, size_t coords) {
+int refill_window(const gbp_terrain *t, size_t coords, bool n_dev = false) {
 #ifndef GBP_REFILL_WINDOW
   return 0;  // the default build has no window
 #else
-  const int block = (int)t->opt_block;
+  const int block = validate_block(t, n_dev);
   const size_t wgs = (size_t)std::max<int64_t>(1, t->opt_waves * 256 / block);
   const size_t cap = std::min<size_t>(t->lds_max, 160 * 1024 / wgs);
   for (int pf = PF_MAX; pf > 0; pf--)
@@ -956,7 +1006,7 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
                       double *t_new, uint32_t *flags, uint32_t *counts, hipStream_t st,
                       const int *n_dev) {
   const TerrainView<ZT> T = view<ZT>(t);
-  const int block = (int)t->opt_block;
+  const int block = validate_block(t, n_dev != nullptr);
   const size_t coords = CM == 1 ? stage_bytes(t->nx, t->ny) : 0;
   const int64_t chunk = (int64_t)1 << 30;
   for (int64_t off = 0; off < n; off += chunk) {
@@ -969,7 +1019,7 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
     if (t->opt_kernel == GBP_KERNEL_DIRECT && !n_dev) {
       // the direct form inlines the state check at five call sites: it gets the
       // whole register file (W = 1) whatever the persistent kernel's budget is
-      const int db = std::min(block, 256);  // k_validate_direct: __launch_bounds__(256)
+      const int db = t->opt_block ? std::min(block, 256) : 256;  // k_validate_direct: __launch_bounds__(256)
       const unsigned g = (unsigned)((m + db - 1) / db);
       hipLaunchKernelGGL((k_validate_direct<ZT, AD, 1, CM == 2 ? 0 : CM>), dim3(g), dim3(db), coords, st, T, m,
                          s + 8 * off, a + 10 * off, d, dir_all, v, sn, tn, flags + off, c);
@@ -983,7 +1033,7 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
       // waves starting with idle lanes that help from the first step
       // (65,536 attempts: 0.084 -> 0.072 ms; 262,144: unchanged)
       const int64_t g = std::max<int64_t>(1, std::min<int64_t>(resident, (m + WAVE - 1) / WAVE));
-      const int pf = refill_window(t, coords);
+      const int pf = refill_window(t, coords, n_dev != nullptr);
       hipLaunchKernelGGL((k_validate_persistent<ZT, AD, W, CM, ONE>), dim3((unsigned)g), dim3(block),
                          coords + rows_bytes(block, pf), st, T, (int)m, s + 8 * off, a + 10 * off, d, dir_all,
                          v, sn, tn, flags + off, c, n_dev, (int)t->opt_helpers, (int)t->opt_xcd_map, pf);
@@ -1009,7 +1059,7 @@ int launch_validate(gbp_terrain *t, int64_t n, const double *s, const double *a,
   // coordinates computed when the affine form is exact; else in LDS only if
   // they fit next to the attempt rows, with room for the W workgroups of 256
   // lanes that share a CU (160 KB per CU); else read from global memory
-  const int cm = validate_coord_mode(t, t->opt_kernel == GBP_KERNEL_DIRECT && !n_dev);
+  const int cm = validate_coord_mode(t, t->opt_kernel == GBP_KERNEL_DIRECT && !n_dev, n_dev != nullptr);
   const bool one = t->one_x && t->one_y;  // straight-line brackets (modes 1, 2 imply it)
   // W = 1 and 2 give the same allocation (the kernel needs < 256 VGPRs)
   if (adaptive) return w >= 4 ? GBP_LV(true, 4) : (w == 3 ? GBP_LV(true, 3) : GBP_LV(true, 2));
@@ -1135,11 +1185,13 @@ extern "C" {
 #ifdef GBP_LOOP_PROF
 // per wave: refill, lane setup / helper plan, sample + isValidState, transition
 // + helper consumption, outputs + s_new ring, whole loop (cycles); tail
-// iterations; iterations
+// iterations; iterations; loop start and end (s_memrealtime); HW_ID; XCC_ID;
+// the wave's entry and its first sample (s_memrealtime): 14 values per wave,
+// wave w of workgroup b at row b * (block / 64) + w
 int gbp_loop_prof_read(unsigned long long *out, int n_waves) {
   if (!out || n_waves < 0 || n_waves > 8192) return GBP_E_INVALID_ARG;
   if (hipDeviceSynchronize() != hipSuccess) return GBP_E_HIP;
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(gbp_loop_prof), sizeof(unsigned long long) * 12 * n_waves) !=
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(gbp_loop_prof), sizeof(unsigned long long) * LP_N * n_waves) !=
       hipSuccess)
     return GBP_E_HIP;
   return GBP_OK;
@@ -1148,7 +1200,8 @@ int gbp_loop_prof_read(unsigned long long *out, int n_waves) {
 
 int gbp_validate_lds_plan(int nx, int ny, int64_t block, int64_t waves, size_t lds_max,
                           int *coord_lds, int *window, size_t *bytes) {
-  if (nx < 2 || ny < 2 || block < WAVE || block > 512 || block % WAVE || waves < 1)
+  // block 0: not set by the caller, the launch chooses (validate_block)
+  if (nx < 2 || ny < 2 || (block && block < WAVE) || block > 512 || block % WAVE || waves < 1)
     return GBP_E_INVALID_ARG;
   gbp_terrain t;  // only the fields the sizing reads
   t.nx = nx;
@@ -1163,7 +1216,7 @@ int gbp_validate_lds_plan(int nx, int ny, int64_t block, int64_t waves, size_t l
   const int pf = refill_window(&t, coords);
   if (coord_lds) *coord_lds = cm == 1;
   if (window) *window = pf;
-  if (bytes) *bytes = coords + rows_bytes((int)block, pf);
+  if (bytes) *bytes = coords + rows_bytes(validate_block(&t, false), pf);
   return GBP_OK;
 }
 
@@ -1362,7 +1415,8 @@ int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value) {
       t->opt_kernel = value;
       return GBP_OK;
     case GBP_OPT_BLOCK:
-      if (value < 64 || value > 512 || value % 64) return GBP_E_INVALID_ARG;
+      // 0: back to not set (validate_block chooses)
+      if (value && (value < 64 || value > 512 || value % 64)) return GBP_E_INVALID_ARG;
       t->opt_block = value;
       return GBP_OK;
     case GBP_OPT_WAVES:
@@ -1401,7 +1455,8 @@ int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value) {
   if (!value) return GBP_E_INVALID_ARG;
   switch (key) {
     case GBP_OPT_KERNEL: *value = t->opt_kernel; return GBP_OK;
-    case GBP_OPT_BLOCK: *value = t->opt_block; return GBP_OK;
+    case GBP_OPT_BLOCK: *value = t->opt_block ? t->opt_block : 256; return GBP_OK;
+    case GBP_OPT_LAUNCH_BLOCK: *value = validate_block(t, false); return GBP_OK;
     case GBP_OPT_WAVES: *value = t->opt_waves; return GBP_OK;
     case GBP_OPT_LDS_COORDS: *value = t->opt_lds_coords; return GBP_OK;
     case GBP_OPT_HELPERS: *value = t->opt_helpers; return GBP_OK;

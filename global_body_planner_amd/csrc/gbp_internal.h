@@ -31,7 +31,7 @@ struct gbp_terrain {
   double *d_dx = nullptr, *d_dy = nullptr, *d_dz = nullptr;
   int num_cus = 256;
   int64_t opt_kernel = GBP_KERNEL_PERSISTENT;
-  int64_t opt_block = 256;
+  int64_t opt_block = 0;            // GBP_OPT_BLOCK; 0: not set, the launch chooses (validate_block)
   int64_t opt_waves = 2;            // register budget of the validate kernels (waves/SIMD)
   int64_t opt_lds_coords = 1;       // stage the coordinate vectors in LDS when they fit
   int64_t opt_helpers = 1;          // idle lanes of a drained wave evaluate owners' next samples

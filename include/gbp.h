@@ -129,7 +129,11 @@ int gbp_terrain_info(const gbp_terrain *t, int *nx, int *ny, int *storage,
 /* engine options (per handle) */
 #define GBP_OPT_KERNEL        1  /* GBP_KERNEL_* for the validate/extend entry points */
 #define GBP_OPT_BLOCK         2  /* threads per workgroup (multiple of 64, <= 512; the
-                                    direct kernel uses min(block, 256))               */
+                                    direct kernel uses min(block, 256)); default 256.
+                                    Until it is set (or once it is set to 0 again) the
+                                    persistent kernel's launch runs 128 lanes where
+                                    2 * waves such workgroups fit a CU's LDS with their
+                                    coordinate vectors: GBP_OPT_LAUNCH_BLOCK           */
 /* keys 3, 6, 7, 11, 12 (grid size, dynamic work sources, chunking, prefix,
    oversubscription) were measured slower than static per-wave slices and removed */
 #define GBP_OPT_WAVES         4  /* register budget: min waves per SIMD (2..4)        */
@@ -155,6 +159,10 @@ int gbp_terrain_info(const gbp_terrain *t, int *nx, int *ny, int *storage,
 #define GBP_OPT_NN_STATS     18  /* 1: the matrix-core search counts its fp64 re-checks
                                     in gbp_plan_status.stat_nn_* (diagnostics: costs
                                     same-address atomics; default 0)                  */
+#define GBP_OPT_LAUNCH_BLOCK 20  /* read-only: threads per workgroup of the next
+                                    persistent validate launch at the current options:
+                                    GBP_OPT_BLOCK where the caller set it, else 128 or
+                                    256 by the rule above                              */
 #define GBP_OPT_REFILL_WINDOW 19 /* read-only: rows per wave of the persistent validate
                                     kernel's prefetch window at the current options
                                     (0: every refill loads its rows itself)           */
@@ -164,7 +172,7 @@ int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value);
 int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value);
 /* The LDS a persistent validate launch would request for an nx x ny terrain
  * with straight-line brackets (no device needed): `block` threads per
- * workgroup, `waves` per SIMD, `lds_max` bytes a workgroup may use.  Outputs
+ * workgroup (0: GBP_OPT_BLOCK not set, the launch's own choice), `waves` per SIMD, `lds_max` bytes a workgroup may use.  Outputs
  * (each may be NULL): coord_lds 1 when the coordinate vectors are staged in
  * LDS, window the rows per wave of the refill's prefetch window (0: every
  * refill loads its rows itself), bytes the dynamic LDS of the launch. */

@@ -11,6 +11,15 @@ Config 3 (synth-rough-1024, 262,144 attempts) and config 2 (synth-rough-256,
 65,536), one launch each after a warm-up launch; with --fresh-batches N the
 profiled launch is the last of 2 N that cycle N distinct resident batches
 (bench.py's inputs: no launch replays cache-warm rows).
+
+From the waves' wall-clock stamps (entry, first sample, end) it also reports
+what a launch's hand-over to the next one leaves on the table: per workgroup,
+the time each ended wave's slot stands empty until the workgroup's last wave
+ends and its LDS is released (`slot_wait_us`: mean per wave, total slot-us per
+launch, and the same split by workgroup size), and the time from the kernel's
+start (its first wave's entry) and from each wave's own entry to that wave's
+first sample (`start_to_first_sample_us`, `entry_to_first_sample_us`: the
+coordinate staging and the first fill).
 """
 import argparse
 import ctypes
@@ -28,6 +37,35 @@ from global_body_planner_amd import terrain_data as td  # noqa: E402
 from global_body_planner_amd import workload as W  # noqa: E402
 
 PHASES = ["refill", "helper_plan", "sample_isvalid", "transition_consume", "outputs_ring"]
+LP_N = 14   # values per wave (gbp_engine.hip gbp_loop_prof)
+
+
+def handover(raw, block):
+    """The hand-over figures of one launch from the per-wave stamps (100 MHz ticks):
+    raw[:, 9] end, raw[:, 12] entry, raw[:, 13] first sample; row = workgroup * nwv + wave."""
+    nwv = max(1, block // 64)
+    a = raw.astype(np.float64)
+    ran = a[:, 12] > 0                       # (a wave with an empty slice still enters and ends)
+    wg = np.arange(a.shape[0]) // nwv
+    end, entry = a[:, 9] * 1e-2, a[:, 12] * 1e-2   # us
+    wait = np.zeros(a.shape[0])
+    for g in np.unique(wg[ran]):
+        m = ran & (wg == g)
+        wait[m] = end[m].max() - end[m]
+    w = wait[ran]
+    t0 = entry[ran].min()
+    first = a[:, 13] * 1e-2
+    stepped = ran & (a[:, 13] > 0)
+    q = (50, 90, 100)
+    return {"block": int(block), "waves_per_workgroup": nwv, "workgroups": int(np.unique(wg[ran]).size),
+            "slot_wait_us": {"mean_per_wave": float(w.mean()), "total_per_launch": float(w.sum()),
+                             "max": float(w.max())},
+            "entry_skew_us": float(entry[ran].max() - t0),
+            "start_to_first_sample_us": {str(k): float(np.percentile(first[stepped] - t0, k)) for k in q},
+            "entry_to_first_sample_us": {"mean": float((first[stepped] - entry[stepped]).mean()),
+                                         **{str(k): float(np.percentile(first[stepped] - entry[stepped], k))
+                                            for k in q}},
+            "kernel_us": float(end[ran].max() - t0)}
 
 
 def run(lib, terrain, batch, seed, opts=(), waves=2048, fresh=1):
@@ -48,10 +86,11 @@ def run(lib, terrain, batch, seed, opts=(), waves=2048, fresh=1):
     else:
         T.validate_pairs(s, act, d, out=out)
     torch.cuda.synchronize()
-    buf = (ctypes.c_ulonglong * (12 * waves))()
+    buf = (ctypes.c_ulonglong * (LP_N * waves))()
     rc = lib.gbp_loop_prof_read(buf, ctypes.c_int(waves))
     assert rc == 0, rc
-    raw = np.frombuffer(buf, dtype=np.uint64).reshape(waves, 12)
+    raw = np.frombuffer(buf, dtype=np.uint64).reshape(waves, LP_N)
+    hand = handover(raw, T.get_option(L.OPT_LAUNCH_BLOCK))
     a = raw.astype(np.float64)
     keep = a[:, 7] > 0
     a, raw = a[keep], raw[keep]
@@ -93,6 +132,7 @@ def run(lib, terrain, batch, seed, opts=(), waves=2048, fresh=1):
     cm = np.array([np.mean(v) for v in cus.values()]) / 1e3
     row["cu_mean_span_us"] = {"n": len(cus), "min": float(cm.min()), "median": float(np.median(cm)),
                               "max": float(cm.max())}
+    row["handover"] = hand
     return row
 
 
