@@ -30,11 +30,14 @@ OPT_LAUNCH_BLOCK = 20
 PLAN_HALT_TARGETS, PLAN_HALT_EXTEND, PLAN_HALT_CONNECT = 1, 2, 4
 PLAN_HALT_STAR, PLAN_HALT_STAR_PAIRS = 8, 16
 KERNEL_DIRECT, KERNEL_PERSISTENT = 0, 1
+SRC_F64_XMAJOR, SRC_F32_GRIDMAP = 0, 1
+E_INVALID_ARG, E_BAD_HANDLE, E_SHAPE, E_UNSUPPORTED = -1, -2, -5, -7
 
 EXPORTS = [
     "gbp_version", "gbp_status_string", "gbp_device_count", "gbp_device_alloc",
     "gbp_device_free", "gbp_memcpy_h2d", "gbp_memcpy_d2h", "gbp_stream_synchronize",
     "gbp_terrain_create", "gbp_terrain_destroy", "gbp_terrain_info",
+    "gbp_terrain_update_dev", "gbp_terrain_update_host", "gbp_terrain_read_host",
     "gbp_terrain_set_option", "gbp_terrain_get_option", "gbp_validate_lds_plan",
     "gbp_height_batch_dev", "gbp_height_batch_host",
     "gbp_normal_batch_dev", "gbp_normal_batch_host",
@@ -68,6 +71,12 @@ class Sampling(ctypes.Structure):
     _fields_ = [("state_flag", ctypes.c_int32), ("state_speed_direction", ctypes.c_int32),
                 ("state_p", ctypes.c_double), ("action_flag", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("action_p", ctypes.c_double)]
+
+
+class Rect(ctypes.Structure):
+    """gbp_rect (include/gbp.h): cells [ix0, ix0 + nx) x [iy0, iy0 + ny)."""
+    _fields_ = [("ix0", ctypes.c_int32), ("iy0", ctypes.c_int32), ("nx", ctypes.c_int32),
+                ("ny", ctypes.c_int32)]
 
 
 class PruneStats(ctypes.Structure):
@@ -120,6 +129,9 @@ def load(path=None):
         "gbp_terrain_create": (I, [I, I, I, P, P, P, P, P, P, I, P]),
         "gbp_terrain_destroy": (I, [P]),
         "gbp_terrain_info": (I, [P, P, P, P, P, P]),
+        "gbp_terrain_update_dev": (I, [P, P, I, I64, P, P, P, P, P, P]),
+        "gbp_terrain_update_host": (I, [P, P, I, I64, P, P, P, P]),
+        "gbp_terrain_read_host": (I, [P, P, I, P]),
         "gbp_terrain_set_option": (I, [P, I, I64]),
         "gbp_terrain_get_option": (I, [P, I, P]),
         "gbp_validate_lds_plan": (I, [I, I, I64, I64, SZ, P, P, P]),

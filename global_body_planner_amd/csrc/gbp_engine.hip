@@ -1391,6 +1391,7 @@ int gbp_terrain_destroy(gbp_terrain *t) {
     if (p) (void)hipFree(p);
   for (auto &w : t->cand_ws)
     if (w.ptr) (void)hipFree(w.ptr);
+  for (auto &u : t->pending) (void)hipEventDestroy(u.done);
   if (t->host_stream) (void)hipStreamDestroy(t->host_stream);
   delete t;
   return GBP_OK;
@@ -2147,13 +2148,15 @@ int gbp_resolve_fragile_host(gbp_terrain *t, int64_t n, const double *s, const d
   if (n < 0 || (n > 0 && (!s || !a || !flags))) return GBP_E_INVALID_ARG;
   if (!direction && direction_all != GBP_FORWARD && direction_all != GBP_REVERSE)
     return GBP_E_INVALID_ARG;
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   int64_t k = 0;
   for (int64_t i = 0; i < n; i++) {
     if (!(flags[i] & GBP_F_FRAGILE)) continue;
     double sn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tn = 0;
     uint32_t f = 0, c = 0;
     const int d = direction ? direction[i] : direction_all;
-    const bool v = gbp_host::pair_check(t->host, s + 8 * i, a + 10 * i, d, adaptive, sn, &tn, &f, &c);
+    const bool v = gbp_host::pair_check(*H, s + 8 * i, a + 10 * i, d, adaptive, sn, &tn, &f, &c);
     if (valid) valid[i] = v ? 1 : 0;
     if (s_new && (f & GBP_F_SNEW_SET)) memcpy(s_new + 8 * i, sn, sizeof sn);
     if (t_new && (f & GBP_F_TNEW_SET)) t_new[i] = tn;
@@ -2170,11 +2173,13 @@ int gbp_resolve_fragile_states_host(gbp_terrain *t, int64_t n, const double *sta
                                     uint32_t *flags, uint32_t *counts, int64_t *n_resolved) {
   if (!valid_handle(t)) return GBP_E_BAD_HANDLE;
   if (n < 0 || (n > 0 && (!states || !flags))) return GBP_E_INVALID_ARG;
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   int64_t k = 0;
   for (int64_t i = 0; i < n; i++) {
     if (!(flags[i] & GBP_F_FRAGILE)) continue;
     gbp_host::Acc acc;
-    const bool v = gbp_host::is_valid_state(t->host, states + 8 * i, phase ? phase[i] : phase_all, acc);
+    const bool v = gbp_host::is_valid_state(*H, states + 8 * i, phase ? phase[i] : phase_all, acc);
     if (valid) valid[i] = v ? 1 : 0;
     flags[i] = acc.flags | (v ? GBP_F_VALID : 0u) | GBP_F_RESOLVED;
     if (counts) counts[i] = (acc.G & 0xFFFFu) | (acc.V << 16);
@@ -2197,6 +2202,8 @@ int gbp_extend_resolve_host(gbp_terrain *t, int64_t n, const double *s_near, con
   if (!valid_handle(t)) return GBP_E_BAD_HANDLE;
   if (n < 0 || (n > 0 && (!s_near || !target || !result || !s_new || !a_new || !flags)))
     return GBP_E_INVALID_ARG;
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   int64_t k = 0;
   for (int64_t i = 0; i < n; i++) {
     if (!(flags[i] & GBP_F_FRAGILE)) continue;
@@ -2221,7 +2228,7 @@ int gbp_extend_resolve_host(gbp_terrain *t, int64_t n, const double *s_near, con
     int found = -1;
     for (int j = 0; j < GBP_NUM_GEN_STATES; j++) {  // rrt.cpp:36-50
       uint32_t f = 0, c = 0;
-      const bool v = gbp_host::pair_check(t->host, sn0, act + 10 * j, d, adaptive, s_test, &t_test, &f, &c);
+      const bool v = gbp_host::pair_check(*H, sn0, act + 10 * j, d, adaptive, s_test, &t_test, &f, &c);
       G += GBP_COUNT_G(c);
       V += GBP_COUNT_V(c);
       ef |= f & (GBP_F_VALID | GBP_F_OOD | GBP_F_NAN | GBP_F_LIMIT);

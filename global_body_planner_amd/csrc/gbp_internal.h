@@ -1,7 +1,8 @@
 // gbp_internal.h — definitions shared by the engine's translation units
 // (gbp_engine.hip: terrain, lookups, pair checks, samplers, extend, NN;
-// gbp_plan.hip: device trees and the device-resident planner loop).  Not
-// part of the C ABI.
+// gbp_plan.hip: device trees and the device-resident planner loop;
+// gbp_terrain.hip: a handle's heights updated in place and its host mirror).
+// Not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,6 +14,7 @@
 #include "gbp.h"
 #include "gbp_device.h"
 #include "host/gbp_host_check.h"
+#include "host/gbp_terrain_patch.h"
 
 constexpr uint64_t GBP_EXTEND_STREAM = 0x45585444ull;  // "EXTD": newConfig's candidate stream
 
@@ -57,7 +59,29 @@ struct gbp_terrain {
     size_t bytes;
   };
   std::vector<StreamWs> cand_ws;
+  // what gbp_terrain_update_dev wrote that `host` has not taken in yet
+  // (host_mirror), one entry per caller stream: the union of that stream's
+  // rectangles and the event recorded behind its last apply launch
+  struct PendingPatch {
+    hipStream_t stream;
+    gbp_patch::Rect rect;
+    hipEvent_t done;
+  };
+  std::vector<PendingPatch> pending;
 };
+
+// brings t->host up to date with the device (gbp_terrain.hip): waits for the
+// pending updates' events, reads the union of their rectangles in one copy
+// and scatters it
+int gbp_internal_mirror_sync(gbp_terrain *t);
+
+// The host copy of the heights, for the glibc re-decisions: every read of
+// t->host goes through here.  With no device update pending it is a flag
+// test; null when bringing the copy up to date failed (a HIP error).
+inline const gbp_host::Terrain *host_mirror(gbp_terrain *t) {
+  if (!t->pending.empty() && gbp_internal_mirror_sync(t) != GBP_OK) return nullptr;
+  return &t->host;
+}
 
 #define HIPCHK(expr)                      \
   do {                                    \

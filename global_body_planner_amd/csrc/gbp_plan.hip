@@ -4335,6 +4335,8 @@ static int resolve_targets(gbp_terrain *t, gbp_plan_ws *w, int64_t batch, hipStr
   if (batch < 1 || batch > w->bmax) return GBP_E_INVALID_ARG;
   int rc;
   std::vector<uint32_t> fl(batch);
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   if ((rc = d2h(fl.data(), w->cflag, batch, s))) return rc;
   HIPCHK(hipStreamSynchronize(s));
   for (int64_t i = 0; i < batch; i++) {
@@ -4343,7 +4345,7 @@ static int resolve_targets(gbp_terrain *t, gbp_plan_ws *w, int64_t batch, hipStr
     if ((rc = d2h(q, w->cand + 8 * i, 8, s))) return rc;
     HIPCHK(hipStreamSynchronize(s));
     gbp_host::Acc acc;
-    const bool v = gbp_host::is_valid_state(t->host, q, GBP_STANCE, acc);
+    const bool v = gbp_host::is_valid_state(*H, q, GBP_STANCE, acc);
     fl[i] = acc.flags | (v ? GBP_F_VALID : 0u) | GBP_F_RESOLVED;
     if ((rc = h2d(w->cflag + i, &fl[i], 1, s))) return rc;
     ++*k;
@@ -4357,6 +4359,8 @@ static int resolve_extend(gbp_terrain *t, gbp_plan_ws *w, const gbp_tree *T, int
                           int adaptive, hipStream_t s, int64_t *k) {
   int rc;
   std::vector<uint32_t> ef(n);
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   if ((rc = d2h(ef.data(), w->ef, n, s))) return rc;
   HIPCHK(hipStreamSynchronize(s));
   for (int64_t i = 0; i < n; i++) {
@@ -4375,7 +4379,7 @@ static int resolve_extend(gbp_terrain *t, gbp_plan_ws *w, const gbp_tree *T, int
     int found = -1;
     for (int j = 0; j < GBP_NUM_GEN_STATES; j++) {
       uint32_t f = 0;
-      const bool v = gbp_host::pair_check(t->host, sn0, act + 10 * j, direction, adaptive, s_test,
+      const bool v = gbp_host::pair_check(*H, sn0, act + 10 * j, direction, adaptive, s_test,
                                           &t_test, &f, nullptr);
       fl |= f & (GBP_F_VALID | GBP_F_OOD | GBP_F_NAN | GBP_F_LIMIT);
       if (v) {
@@ -4413,6 +4417,8 @@ static int resolve_connect(gbp_terrain *t, gbp_plan_ws *w, const gbp_tree *T, co
   if (!tree_ok(O)) return GBP_E_BAD_HANDLE;
   int rc;
   const int64_t n = st.n_added, base = st.added_base;
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   const int cdir = direction == GBP_FORWARD ? GBP_REVERSE : GBP_FORWARD;
   std::vector<uint32_t> kf(n);
   if ((rc = d2h(kf.data(), w->kf, n, s))) return rc;
@@ -4427,7 +4433,7 @@ static int resolve_connect(gbp_terrain *t, gbp_plan_ws *w, const gbp_tree *T, co
     HIPCHK(hipStreamSynchronize(s));
     const double t_s = gbp_host::pose_distance(sq, se) / V_NOM;
     uint32_t f = 0;
-    const int32_t r = gbp_host::attempt_connect(t->host, se, sq, t_s, sn, an, cdir, adaptive,
+    const int32_t r = gbp_host::attempt_connect(*H, se, sq, t_s, sn, an, cdir, adaptive,
                                                 GBP_CONNECT_MAX_DEPTH, &f);
     const uint32_t fr = f | GBP_F_RESOLVED;
     if ((rc = h2d(w->kres + i, &r, 1, s)) || (rc = h2d(w->kan + 10 * i, an, 10, s)) ||
@@ -4445,6 +4451,8 @@ static int resolve_star(gbp_terrain *t, gbp_plan_ws *w, const gbp_plan_status &s
                         int adaptive, hipStream_t s, int64_t *k) {
   int rc;
   const int64_t n = st.star_rows;
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   std::vector<uint32_t> rf(n);
   const gbp_plan_ws::StarSet &S = w->ss[st.halt_half & 1];
   if (n && (rc = d2h(rf.data(), S.srf, n, s))) return rc;
@@ -4455,7 +4463,7 @@ static int resolve_star(gbp_terrain *t, gbp_plan_ws *w, const gbp_plan_status &s
     if ((rc = d2h(sv, S.srs + 8 * i, 8, s)) || (rc = d2h(av, S.sra + 10 * i, 10, s))) return rc;
     HIPCHK(hipStreamSynchronize(s));
     uint32_t f = 0;
-    const bool v = gbp_host::pair_check(t->host, sv, av, direction, adaptive, sn, &tn, &f, nullptr);
+    const bool v = gbp_host::pair_check(*H, sv, av, direction, adaptive, sn, &tn, &f, nullptr);
     const uint32_t fr = (f & ~GBP_F_FRAGILE) | (v ? GBP_F_VALID : 0u) | GBP_F_RESOLVED;
     if ((rc = h2d(S.srf + i, &fr, 1, s))) return rc;
     HIPCHK(hipStreamSynchronize(s));
@@ -4564,6 +4572,8 @@ int gbp_shortcut_paths_host(gbp_terrain *t, int64_t n_paths, const int64_t *path
   HIPCHK(hipStreamSynchronize(s));
   uint8_t *reached = tab.data();
   const uint32_t *fl = (const uint32_t *)(tab.data() + fl_at);
+  const gbp_host::Terrain *H = host_mirror(t);
+  if (!H) return GBP_E_HIP;
   const gbp_shortcut::CostWeights cw{cost_add_yaw_flag, length_weight, yaw_weight};
   int64_t item = 0, resolved = 0, kept = 0;
   for (int64_t p = 0; p < n_paths; p++) {
@@ -4583,7 +4593,7 @@ int gbp_shortcut_paths_host(gbp_terrain *t, int64_t n_paths, const int64_t *path
         if (!(t_s <= KINEMATICS_RES)) {
           gbp_host::connect_action(si, sj, t_s, an);
           if (gbp_host::is_valid_action(an))
-            ok = gbp_host::pair_check(t->host, si, an, GBP_FORWARD, adaptive, sn, &tn, &f, nullptr);
+            ok = gbp_host::pair_check(*H, si, an, GBP_FORWARD, adaptive, sn, &tn, &f, nullptr);
         }
         reached[it] = ok ? 1 : 0;
         resolved++;

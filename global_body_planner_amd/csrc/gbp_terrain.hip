@@ -1,0 +1,372 @@
+// gbp_terrain.hip — a terrain handle's heights updated in place
+// (gbp_terrain_update_dev / _host, gbp_terrain_read_host) and the lazy host
+// mirror behind host_mirror (gbp_internal.h).  A translation unit of its own:
+// the objects of gbp_engine.hip and gbp_plan.hip do not depend on it.
+//
+// Heights lie in HBM as x-pairs (gbp_device.h TerrainView): zp[2 (ix ny + iy)
+// + {0, 1}] = z[ix][iy], z[ix + 1][iy] for ix < nx - 1, so a cell's height is
+// held by slot 0 of pair row ix and by slot 1 of pair row ix - 1.  The patch
+// kernel is output-centric: one thread per (pair row, iy) writes the slots of
+// that pair the rectangle covers, both in one 2-element store, a single slot
+// at the rectangle's first and last pair row.  No two threads write one
+// address.  The engine-free index rules are host/gbp_terrain_patch.{h,cpp}.
+
+#include "gbp_internal.h"
+
+namespace {
+
+constexpr int PATCH_BLOCK = 256;
+constexpr int PATCH_TILE = 64;  // GBP_SRC_F32_GRIDMAP: 64 x 64 outputs from a 64 x 65 tile
+
+struct PatchArgs {
+  void *zp;             // the handle's x-pairs
+  double *lay[3];       // its slope layers [nx][ny]
+  const void *src[4];   // z, dx, dy, dz in the source layout (dx..dz null: not given)
+  int64_t ld, off;      // a cell's element = the layout's index (gbp_patch::src_index) - off
+  int NX, NY;
+  int ix0, iy0, pnx, pny;
+  int r0, r1;           // rows [r0, r1) = [max(ix0 - 1, 0), ix0 + pnx): pair rows of the
+                        // heights (those below NX - 1), cell rows of the layers (from ix0)
+  const int32_t *status;  // null, or the check launch's word: 1 = write nothing
+};
+
+template <class ZT>
+struct Pair;
+template <>
+struct Pair<float> {
+  using type = float2;
+};
+template <>
+struct Pair<double> {
+  using type = double2;
+};
+
+// gbp_patch::src_index on the device
+template <int SRC>
+__device__ __forceinline__ int64_t src_at(const PatchArgs &A, int ix, int iy) {
+  return (SRC == GBP_SRC_F32_GRIDMAP
+              ? (int64_t)(A.NX - 1 - ix) + (int64_t)(A.NY - 1 - iy) * A.ld
+              : (int64_t)(ix - A.ix0) * A.ld + (int64_t)(iy - A.iy0)) -
+         A.off;
+}
+
+// pair row p at iy: slot 0 = z[p][iy] when row p is in the rectangle, slot 1 =
+// z[p + 1][iy] when row p + 1 is; the other slot keeps its value
+template <class ZT>
+__device__ __forceinline__ void put_pair(const PatchArgs &A, int p, int iy, bool lo, bool hi,
+                                         double v0, double v1) {
+  ZT *q = (ZT *)A.zp + 2 * ((int64_t)p * A.NY + iy);
+  if (lo && hi) {
+    typename Pair<ZT>::type v;
+    v.x = (ZT)v0;
+    v.y = (ZT)v1;
+    *(typename Pair<ZT>::type *)q = v;
+  } else if (lo) {
+    q[0] = (ZT)v0;
+  } else if (hi) {
+    q[1] = (ZT)v1;
+  }
+}
+
+// blockIdx.z = 0: the heights; 1..3: slope layer dx / dy / dz (launched only
+// when given).  GBP_SRC_F64_XMAJOR: lanes along iy on both sides, rows by
+// blockIdx.y.  GBP_SRC_F32_GRIDMAP is contiguous along x and reversed on both
+// axes, the destination contiguous along y: a workgroup loads rows [rt, rt +
+// 65) x 64 columns with lanes along x into LDS (pitch 65: the transposed read
+// is conflict-free), then writes 64 pair rows with lanes along y.
+template <class ZT, int SRC>
+__global__ __launch_bounds__(PATCH_BLOCK) void k_terrain_patch(const PatchArgs A) {
+  if (A.status && *A.status) return;  // rejected by k_terrain_check
+  const int which = blockIdx.z;
+  const int xe = A.ix0 + A.pnx, ye = A.iy0 + A.pny;
+  if constexpr (SRC == GBP_SRC_F32_GRIDMAP) {
+    __shared__ float tile[PATCH_TILE][PATCH_TILE + 1];
+    const float *src = (const float *)A.src[which];
+    const int rt = A.r0 + (int)blockIdx.y * PATCH_TILE, jt = A.iy0 + (int)blockIdx.x * PATCH_TILE;
+    for (int e = threadIdx.x; e < PATCH_TILE * (PATCH_TILE + 1); e += PATCH_BLOCK) {
+      const int li = e % (PATCH_TILE + 1), lj = e / (PATCH_TILE + 1);
+      const int ix = rt + li, iy = jt + lj;
+      if (ix >= A.ix0 && ix < xe && iy < ye) tile[lj][li] = src[src_at<SRC>(A, ix, iy)];
+    }
+    __syncthreads();
+    const int lj = threadIdx.x % PATCH_TILE, iy = jt + lj;
+    if (iy >= ye) return;
+    for (int li = threadIdx.x / PATCH_TILE; li < PATCH_TILE; li += PATCH_BLOCK / PATCH_TILE) {
+      const int r = rt + li;
+      if (r >= A.r1) break;
+      if (which == 0) {
+        if (r >= A.NX - 1) break;
+        const bool lo = r >= A.ix0, hi = r + 1 < xe;
+        put_pair<ZT>(A, r, iy, lo, hi, lo ? (double)tile[lj][li] : 0.0,
+                     hi ? (double)tile[lj][li + 1] : 0.0);
+      } else if (r >= A.ix0) {
+        A.lay[which - 1][(int64_t)r * A.NY + iy] = (double)tile[lj][li];
+      }
+    }
+  } else {
+    const double *src = (const double *)A.src[which];
+    const int iy = A.iy0 + (int)(blockIdx.x * PATCH_BLOCK + threadIdx.x);
+    if (iy >= ye) return;
+    for (int r = A.r0 + (int)blockIdx.y; r < A.r1; r += (int)gridDim.y) {
+      if (which == 0) {
+        if (r >= A.NX - 1) break;
+        const bool lo = r >= A.ix0, hi = r + 1 < xe;
+        put_pair<ZT>(A, r, iy, lo, hi, lo ? src[src_at<SRC>(A, r, iy)] : 0.0,
+                     hi ? src[src_at<SRC>(A, r + 1, iy)] : 0.0);
+      } else if (r >= A.ix0) {
+        A.lay[which - 1][(int64_t)r * A.NY + iy] = src[src_at<SRC>(A, r, iy)];
+      }
+    }
+  }
+}
+
+// an fp64 patch for an fp32 handle: status[0] = 1 when a height is neither
+// NaN nor float-representable (status[0] was zeroed on the stream before)
+__global__ __launch_bounds__(PATCH_BLOCK) void k_terrain_check(const double *src, int64_t ld,
+                                                               int pnx, int pny,
+                                                               int32_t *status) {
+  const int64_t n = (int64_t)pnx * pny;
+  bool bad = false;
+  for (int64_t e = (int64_t)blockIdx.x * PATCH_BLOCK + threadIdx.x; e < n;
+       e += (int64_t)gridDim.x * PATCH_BLOCK) {
+    const double v = src[(e / pny) * ld + (e % pny)];
+    bad |= !(v != v) && (double)(float)v != v;
+  }
+  if (bad) status[0] = 1;
+}
+
+// out[i][j] = z[ix0 + i][iy0 + j] from the chosen copy (gbp_terrain_read_host)
+template <class ZT>
+__global__ __launch_bounds__(PATCH_BLOCK) void k_terrain_read(const ZT *zp, double *out, int NX,
+                                                              int NY, int ix0, int iy0, int rnx,
+                                                              int rny, int copy) {
+  const int j = (int)(blockIdx.x * PATCH_BLOCK + threadIdx.x);
+  if (j >= rny) return;
+  const int iy = iy0 + j;
+  for (int i = blockIdx.y; i < rnx; i += (int)gridDim.y) {
+    const int ix = ix0 + i;
+    int p, slot;
+    if (copy == 0) {
+      p = ix < NX - 1 ? ix : NX - 2;
+      slot = ix < NX - 1 ? 0 : 1;
+    } else {
+      p = ix > 0 ? ix - 1 : 0;
+      slot = ix > 0 ? 1 : 0;
+    }
+    out[(int64_t)i * rny + j] = (double)zp[2 * ((int64_t)p * NY + iy) + slot];
+  }
+}
+
+bool valid_handle(const gbp_terrain *t) { return t != nullptr && t->d_z != nullptr; }
+
+unsigned rows_grid(int rows) { return (unsigned)std::min(std::max(rows, 1), 65535); }
+
+// the apply launch for a checked rectangle and source
+int launch_patch(gbp_terrain *t, const gbp_patch::Rect &q, int layout, int64_t ld, int64_t off,
+                 const void *z, const void *dx, const void *dy, const void *dz,
+                 const int32_t *status, hipStream_t st) {
+  PatchArgs A;
+  A.zp = t->d_z;
+  A.lay[0] = t->d_dx;
+  A.lay[1] = t->d_dy;
+  A.lay[2] = t->d_dz;
+  A.src[0] = z;
+  A.src[1] = dx;
+  A.src[2] = dy;
+  A.src[3] = dz;
+  A.ld = ld;
+  A.off = off;
+  A.NX = t->nx;
+  A.NY = t->ny;
+  A.ix0 = q.ix0;
+  A.iy0 = q.iy0;
+  A.pnx = q.nx;
+  A.pny = q.ny;
+  A.r0 = std::max(q.ix0 - 1, 0);
+  A.r1 = q.ix0 + q.nx;
+  A.status = status;
+  const int rows = A.r1 - A.r0;
+  const unsigned nz = dx ? 4 : 1;
+  const bool f32 = t->storage == GBP_STORAGE_F32;
+  if (layout == GBP_SRC_F32_GRIDMAP) {
+    const dim3 grid((unsigned)((q.ny + PATCH_TILE - 1) / PATCH_TILE),
+                    (unsigned)((rows + PATCH_TILE - 1) / PATCH_TILE), nz);
+    if (grid.y > 65535u) return GBP_E_SHAPE;
+    if (f32)
+      k_terrain_patch<float, GBP_SRC_F32_GRIDMAP><<<grid, PATCH_BLOCK, 0, st>>>(A);
+    else
+      k_terrain_patch<double, GBP_SRC_F32_GRIDMAP><<<grid, PATCH_BLOCK, 0, st>>>(A);
+  } else {
+    const dim3 grid((unsigned)((q.ny + PATCH_BLOCK - 1) / PATCH_BLOCK), rows_grid(rows), nz);
+    if (f32)
+      k_terrain_patch<float, GBP_SRC_F64_XMAJOR><<<grid, PATCH_BLOCK, 0, st>>>(A);
+    else
+      k_terrain_patch<double, GBP_SRC_F64_XMAJOR><<<grid, PATCH_BLOCK, 0, st>>>(A);
+  }
+  HIPCHK(hipGetLastError());
+  return GBP_OK;
+}
+
+// the argument checks both entries share
+int check_args(const gbp_terrain *t, const gbp_rect *r, int layout, int64_t ld, const void *z,
+               const void *dx, const void *dy, const void *dz, gbp_patch::Rect *q) {
+  int rc = gbp_patch::resolve_rect(t->nx, t->ny, r, q);
+  if (rc) return rc;
+  if ((rc = gbp_patch::check_source(layout, t->nx, *q, ld, z))) return rc;
+  if ((dx == nullptr) != (dy == nullptr) || (dx == nullptr) != (dz == nullptr))
+    return GBP_E_INVALID_ARG;
+  if (dx && !t->d_dx) return GBP_E_INVALID_ARG;
+  return GBP_OK;
+}
+
+// later work on the handle's host stream runs after every pending device update
+int wait_pending(gbp_terrain *t) {
+  for (auto &u : t->pending) HIPCHK(hipStreamWaitEvent(t->host_stream, u.done, 0));
+  return GBP_OK;
+}
+
+// the rectangle's heights from the chosen copy into host out[q.nx][q.ny], on
+// the host stream, synchronous
+int read_rect(gbp_terrain *t, const gbp_patch::Rect &q, int copy, double *out) {
+  hipStream_t st = t->host_stream;
+  const size_t n = (size_t)q.nx * q.ny;
+  DevBuf buf;
+  double *d;
+  int rc = stage_buf(buf, [&](Stage &S) { S.take(d, n); });
+  if (rc) return rc;
+  const dim3 grid((unsigned)((q.ny + PATCH_BLOCK - 1) / PATCH_BLOCK), rows_grid(q.nx));
+  if (t->storage == GBP_STORAGE_F32)
+    k_terrain_read<float><<<grid, PATCH_BLOCK, 0, st>>>((const float *)t->d_z, d, t->nx, t->ny,
+                                                        q.ix0, q.iy0, q.nx, q.ny, copy);
+  else
+    k_terrain_read<double><<<grid, PATCH_BLOCK, 0, st>>>((const double *)t->d_z, d, t->nx, t->ny,
+                                                         q.ix0, q.iy0, q.nx, q.ny, copy);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, d, n * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return GBP_OK;
+}
+
+// `rows` runs of `width` bytes, `spitch` apart in the host source, packed on the device
+int stage_rows(void *dst, const void *src, size_t width, size_t spitch, size_t rows,
+               hipStream_t st) {
+  if (spitch == width || rows == 1)
+    HIPCHK(hipMemcpyAsync(dst, src, width * rows, hipMemcpyHostToDevice, st));
+  else
+    HIPCHK(hipMemcpy2DAsync(dst, width, src, spitch, width, rows, hipMemcpyHostToDevice, st));
+  return GBP_OK;
+}
+
+constexpr size_t MAX_PENDING = 64;  // caller streams with updates the mirror has not taken in
+
+}  // namespace
+
+__attribute__((visibility("hidden"))) int gbp_internal_mirror_sync(gbp_terrain *t) {
+  if (t->pending.empty()) return GBP_OK;
+  DeviceGuard g(t->device);
+  gbp_patch::Rect u = t->pending[0].rect;
+  for (auto &p : t->pending) u = gbp_patch::rect_union(u, p.rect);
+  int rc = wait_pending(t);
+  if (rc) return rc;
+  std::vector<double> h((size_t)u.nx * u.ny);
+  if ((rc = read_rect(t, u, 0, h.data()))) return rc;
+  // the read-back is x-major with ld = u.ny
+  gbp_patch::scatter(t->host.z.data(), t->nx, t->ny, u, GBP_SRC_F64_XMAJOR, u.ny, h.data(), false);
+  for (auto &p : t->pending) (void)hipEventDestroy(p.done);
+  t->pending.clear();
+  return GBP_OK;
+}
+
+extern "C" {
+
+int gbp_terrain_update_dev(gbp_terrain *t, const gbp_rect *r, int src_layout, int64_t ld,
+                           const void *z, const void *dx, const void *dy, const void *dz,
+                           int32_t *status, gbp_stream stream) {
+  if (!valid_handle(t)) return GBP_E_BAD_HANDLE;
+  gbp_patch::Rect q;
+  int rc = check_args(t, r, src_layout, ld, z, dx, dy, dz, &q);
+  if (rc) return rc;
+  const bool need_check = src_layout == GBP_SRC_F64_XMAJOR && t->storage == GBP_STORAGE_F32;
+  if (need_check && !status) return GBP_E_INVALID_ARG;
+  DeviceGuard g(t->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (status) HIPCHK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+  if (need_check) {
+    const int64_t n = (int64_t)q.nx * q.ny;
+    k_terrain_check<<<grid_for(n, PATCH_BLOCK, 4096), PATCH_BLOCK, 0, st>>>(
+        (const double *)z, ld, q.nx, q.ny, status);
+    HIPCHK(hipGetLastError());
+  }
+  if ((rc = launch_patch(t, q, src_layout, ld, 0, z, dx, dy, dz, need_check ? status : nullptr, st)))
+    return rc;
+  // the mirror takes the rectangle in lazily (host_mirror), a rejected one too:
+  // its heights are as they were, reading them again changes nothing
+  for (auto &u : t->pending)
+    if (u.stream == st) {
+      HIPCHK(hipEventRecord(u.done, st));  // behind the stream's earlier updates as well
+      u.rect = gbp_patch::rect_union(u.rect, q);
+      return GBP_OK;
+    }
+  if (t->pending.size() >= MAX_PENDING && (rc = gbp_internal_mirror_sync(t))) return rc;
+  hipEvent_t ev;
+  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  if (hipEventRecord(ev, st) != hipSuccess) {
+    (void)hipEventDestroy(ev);
+    return GBP_E_HIP;
+  }
+  t->pending.push_back({st, q, ev});
+  return GBP_OK;
+}
+
+int gbp_terrain_update_host(gbp_terrain *t, const gbp_rect *r, int src_layout, int64_t ld,
+                            const void *z, const void *dx, const void *dy, const void *dz) {
+  if (!valid_handle(t)) return GBP_E_BAD_HANDLE;
+  gbp_patch::Rect q;
+  int rc = check_args(t, r, src_layout, ld, z, dx, dy, dz, &q);
+  if (rc) return rc;
+  // all or nothing: the patch is checked before anything is staged
+  if ((rc = gbp_patch::check_patch(t->nx, t->ny, t->storage, r, src_layout, ld, z, &q))) return rc;
+  DeviceGuard g(t->device);
+  hipStream_t st = t->host_stream;
+  if ((rc = wait_pending(t))) return rc;
+  // the rectangle's sub-block of each source array, packed: ld = its own width
+  const bool grid_map = src_layout == GBP_SRC_F32_GRIDMAP;
+  const size_t esz = grid_map ? sizeof(float) : sizeof(double);
+  const size_t cells = (size_t)q.nx * q.ny;
+  const void *hsrc[4] = {z, dx, dy, dz};
+  char *dsrc[4] = {nullptr, nullptr, nullptr, nullptr};
+  const int nsrc = dx ? 4 : 1;
+  DevBuf buf;
+  rc = stage_buf(buf, [&](Stage &S) {
+    for (int k = 0; k < nsrc; k++) S.take(dsrc[k], cells * esz);
+  });
+  if (rc) return rc;
+  // GBP_SRC_F32_GRIDMAP: source columns [a0, a0 + q.nx) of rows [b0, b0 + q.ny)
+  const int64_t a0 = t->nx - q.ix0 - q.nx, b0 = t->ny - q.iy0 - q.ny;
+  const int64_t sld = grid_map ? q.nx : q.ny, off = grid_map ? a0 + b0 * sld : 0;
+  for (int k = 0; k < nsrc; k++) {
+    const char *s = (const char *)hsrc[k] + (grid_map ? (size_t)(a0 + b0 * ld) * esz : 0);
+    rc = stage_rows(dsrc[k], s, (size_t)sld * esz, (size_t)ld * esz,
+                    grid_map ? (size_t)q.ny : (size_t)q.nx, st);
+    if (rc) return rc;
+  }
+  if ((rc = launch_patch(t, q, src_layout, sld, off, dsrc[0], dsrc[1], dsrc[2], dsrc[3], nullptr, st)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  gbp_patch::scatter(t->host.z.data(), t->nx, t->ny, q, src_layout, ld, z,
+                     t->storage == GBP_STORAGE_F32);
+  return GBP_OK;
+}
+
+int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z) {
+  if (!valid_handle(t)) return GBP_E_BAD_HANDLE;
+  gbp_patch::Rect q;
+  int rc = gbp_patch::resolve_rect(t->nx, t->ny, r, &q);
+  if (rc) return rc;
+  if ((copy != 0 && copy != 1) || !z) return GBP_E_INVALID_ARG;
+  DeviceGuard g(t->device);
+  if ((rc = wait_pending(t))) return rc;
+  return read_rect(t, q, copy, z);
+}
+
+}  // extern "C"

@@ -157,7 +157,7 @@ FastTerrainMap FastTerrainMap::borrow(gbp_terrain *handle) {
 }
 
 FastTerrainMap::FastTerrainMap(FastTerrainMap &&o) noexcept
-    : device_(o.device_), handle_(o.handle_), owned_(o.owned_), x_size_(o.x_size_),
+    : device_(o.device_), handle_(o.handle_), owned_(o.owned_), slopes_(o.slopes_), x_size_(o.x_size_),
       y_size_(o.y_size_), x_data_(std::move(o.x_data_)), y_data_(std::move(o.y_data_)) {
   o.handle_ = nullptr;
 }
@@ -204,10 +204,45 @@ void FastTerrainMap::loadDataFlat(int x_size, int y_size, const double *x, const
   if (handle_ && owned_) gbp_terrain_destroy(handle_);
   handle_ = h;
   owned_ = true;
+  slopes_ = dx != nullptr;
   x_size_ = x_size;
   y_size_ = y_size;
   x_data_.assign(x, x + x_size);
   y_data_.assign(y, y + y_size);
+}
+
+void FastTerrainMap::updateDataFlat(int ix0, int iy0, int pnx, int pny, const double *z,
+                                    const double *dx, const double *dy, const double *dz) {
+  const gbp_rect r{ix0, iy0, pnx, pny};
+  chk(gbp_terrain_update_host(handle_, &r, GBP_SRC_F64_XMAJOR, pny, z, dx, dy, dz),
+      "gbp_terrain_update_host");
+}
+
+void FastTerrainMap::updateData(const std::vector<std::vector<double>> &z_data,
+                                const std::vector<std::vector<double>> &dx_data,
+                                const std::vector<std::vector<double>> &dy_data,
+                                const std::vector<std::vector<double>> &dz_data) {
+  const size_t cells = (size_t)x_size_ * y_size_;
+  std::vector<double> z(cells), dx, dy, dz;
+  const bool slopes = dx_data.size() == (size_t)x_size_ && dy_data.size() == (size_t)x_size_ &&
+                      dz_data.size() == (size_t)x_size_;
+  if (slopes) {
+    dx.resize(cells);
+    dy.resize(cells);
+    dz.resize(cells);
+  }
+  for (int i = 0; i < x_size_; i++)
+    for (int j = 0; j < y_size_; j++) {
+      const size_t k = (size_t)i * y_size_ + j;
+      z[k] = z_data.at(i).at(j);
+      if (slopes) {
+        dx[k] = dx_data[i].at(j);
+        dy[k] = dy_data[i].at(j);
+        dz[k] = dz_data[i].at(j);
+      }
+    }
+  updateDataFlat(0, 0, x_size_, y_size_, z.data(), slopes ? dx.data() : nullptr,
+                 slopes ? dy.data() : nullptr, slopes ? dz.data() : nullptr);
 }
 
 double FastTerrainMap::getGroundHeight(const double x, const double y) {

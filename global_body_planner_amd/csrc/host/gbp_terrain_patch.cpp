@@ -1,0 +1,79 @@
+// gbp_terrain_patch.cpp — see gbp_terrain_patch.h
+#include "gbp_terrain_patch.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace gbp_patch {
+
+int resolve_rect(int NX, int NY, const gbp_rect *r, Rect *out) {
+  Rect q;
+  if (r) {
+    q.ix0 = r->ix0;
+    q.iy0 = r->iy0;
+    q.nx = r->nx;
+    q.ny = r->ny;
+  } else {
+    q.nx = NX;
+    q.ny = NY;
+  }
+  if (q.nx <= 0 || q.ny <= 0 || q.ix0 < 0 || q.iy0 < 0) return GBP_E_SHAPE;
+  if ((int64_t)q.ix0 + q.nx > NX || (int64_t)q.iy0 + q.ny > NY) return GBP_E_SHAPE;
+  *out = q;
+  return GBP_OK;
+}
+
+void pair_rows(int NX, const Rect &r, int *p0, int *p1) {
+  *p0 = std::max(r.ix0 - 1, 0);
+  *p1 = std::min(r.ix0 + r.nx, NX - 1);
+}
+
+Rect rect_union(const Rect &a, const Rect &b) {
+  Rect u;
+  u.ix0 = std::min(a.ix0, b.ix0);
+  u.iy0 = std::min(a.iy0, b.iy0);
+  u.nx = std::max(a.ix0 + a.nx, b.ix0 + b.nx) - u.ix0;
+  u.ny = std::max(a.iy0 + a.ny, b.iy0 + b.ny) - u.iy0;
+  return u;
+}
+
+int check_source(int layout, int NX, const Rect &r, int64_t ld, const void *src) {
+  if (layout != GBP_SRC_F64_XMAJOR && layout != GBP_SRC_F32_GRIDMAP) return GBP_E_INVALID_ARG;
+  if (!src) return GBP_E_INVALID_ARG;
+  if (ld < (layout == GBP_SRC_F32_GRIDMAP ? (int64_t)NX : (int64_t)r.ny)) return GBP_E_SHAPE;
+  return GBP_OK;
+}
+
+bool round_trips(int layout, int NX, int NY, const Rect &r, int64_t ld, const void *src) {
+  if (layout == GBP_SRC_F32_GRIDMAP) return true;
+  for (int ix = r.ix0; ix < r.ix0 + r.nx; ix++)
+    for (int iy = r.iy0; iy < r.iy0 + r.ny; iy++) {
+      const double v = src_value(layout, NX, NY, r, ld, src, ix, iy);
+      if (!std::isnan(v) && (double)(float)v != v) return false;
+    }
+  return true;
+}
+
+int check_patch(int NX, int NY, int storage, const gbp_rect *r, int layout, int64_t ld,
+                const void *src, Rect *out) {
+  Rect q;
+  int rc = resolve_rect(NX, NY, r, &q);
+  if (rc) return rc;
+  rc = check_source(layout, NX, q, ld, src);
+  if (rc) return rc;
+  if (storage == GBP_STORAGE_F32 && !round_trips(layout, NX, NY, q, ld, src))
+    return GBP_E_UNSUPPORTED;
+  *out = q;
+  return GBP_OK;
+}
+
+void scatter(double *mirror, int NX, int NY, const Rect &r, int layout, int64_t ld,
+             const void *src, bool f32) {
+  for (int ix = r.ix0; ix < r.ix0 + r.nx; ix++)
+    for (int iy = r.iy0; iy < r.iy0 + r.ny; iy++) {
+      const double v = src_value(layout, NX, NY, r, ld, src, ix, iy);
+      mirror[(int64_t)ix * NY + iy] = f32 ? (double)(float)v : v;
+    }
+}
+
+}  // namespace gbp_patch

@@ -107,6 +107,66 @@ class Terrain:
         check(self._lib.gbp_terrain_get_option(self._h, int(key), ctypes.byref(v)), "get_option")
         return v.value
 
+    # ---- heights updated in place ----------------------------------------------
+    def update(self, z, ix0=0, iy0=0, dx=None, dy=None, dz=None, layout=L.SRC_F64_XMAJOR,
+               shape=None):
+        """Replace the heights (and, given all three, the slope layers) of a
+        rectangle of cells in place (gbp_terrain_update_*): options, sampling,
+        workspaces and PlanWorkspace objects of the handle stay.
+
+        layout SRC_F64_XMAJOR: z (and dx / dy / dz) are float64 [pnx][pny], the
+        rectangle's cells from (ix0, iy0).  layout SRC_F32_GRIDMAP: float32
+        [NY][ld], ld >= NX, a whole grid_map layer as it lies in memory
+        (z[c][r] = layer(r, c), cell (ix, iy) at [NY-1-iy][NX-1-ix]); the
+        rectangle is `shape` = (pnx, pny) cells from (ix0, iy0), to the map's
+        far corner when None.
+
+        numpy input takes the synchronous host entry (a patch an fp32 handle
+        cannot hold raises GbpError with status E_UNSUPPORTED and changes
+        nothing).  Device tensors take the device entry on the current torch
+        stream and return the int32 status tensor ([0] = 0 applied, 1
+        rejected), which is read only after that stream is synchronised."""
+        on_dev = isinstance(z, torch.Tensor) and z.is_cuda
+        dt_np, dt_t = (np.float32, torch.float32) if layout == L.SRC_F32_GRIDMAP \
+            else (np.float64, torch.float64)
+        arrs = []
+        for v in (z, dx, dy, dz):
+            if v is None:
+                arrs.append(None)
+            elif on_dev:
+                arrs.append(v.to(device=self.torch_device, dtype=dt_t).contiguous())
+            else:
+                arrs.append(np.ascontiguousarray(_np(v), dt_np))
+        if arrs[0].ndim != 2 or any(v is not None and v.shape != arrs[0].shape for v in arrs[1:]):
+            raise ValueError("z, dx, dy, dz must be 2-D arrays of one shape")
+        if layout == L.SRC_F32_GRIDMAP:
+            if arrs[0].shape[0] != self.ny:
+                raise ValueError(f"a grid_map layer is [{self.ny}][ld], got {tuple(arrs[0].shape)}")
+            pnx, pny = shape if shape is not None else (self.nx - ix0, self.ny - iy0)
+        else:
+            pnx, pny = arrs[0].shape
+        rect = L.Rect(int(ix0), int(iy0), int(pnx), int(pny))
+        ld = int(arrs[0].shape[1])
+        if on_dev:
+            status = self._empty(1, torch.int32)
+            check(self._lib.gbp_terrain_update_dev(self._h, ctypes.byref(rect), int(layout), ld,
+                                                   *[_ptr(v) for v in arrs], _ptr(status),
+                                                   _stream(self.device)), "update")
+            return status
+        check(self._lib.gbp_terrain_update_host(self._h, ctypes.byref(rect), int(layout), ld,
+                                                *[_np_ptr(v) for v in arrs]), "update")
+        return None
+
+    def read(self, rect=None, copy=0):
+        """The heights the device holds (gbp_terrain_read_host), float64
+        [nx][ny] of rect = (ix0, iy0, nx, ny), the whole map when None.  A
+        height lies in up to two x-pairs: copy 0 / 1 choose which is read."""
+        r = L.Rect(0, 0, self.nx, self.ny) if rect is None else L.Rect(*[int(v) for v in rect])
+        out = np.empty((max(r.nx, 0), max(r.ny, 0)), np.float64)
+        check(self._lib.gbp_terrain_read_host(self._h, ctypes.byref(r), int(copy), _np_ptr(out)),
+              "read")
+        return out
+
     # ---- helpers --------------------------------------------------------------
     def _dev(self, t, dtype, shape_tail=None, name="tensor"):
         if not isinstance(t, torch.Tensor):

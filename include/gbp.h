@@ -126,6 +126,56 @@ int gbp_terrain_destroy(gbp_terrain *t);
 int gbp_terrain_info(const gbp_terrain *t, int *nx, int *ny, int *storage,
                      double bounds[4], int *device);
 
+/* ---- a terrain's heights updated in place ----------------------------------
+ * The node loads every new map into the same FastTerrainMap
+ * (global_body_planner.cpp:37-44).  An update replaces the heights (and, when
+ * given, the slope layers) of a rectangle of cells, or of the whole map, of a
+ * living handle.  Geometry, storage type, options, sampling, workspaces and
+ * the gbp_plan_ws objects created for the handle are untouched: afterwards the
+ * handle is bit for bit what gbp_terrain_create would have made of the patched
+ * map with the same storage and options.  An update never changes the storage
+ * type: a changed geometry or storage stays a new gbp_terrain_create. */
+typedef struct gbp_rect { int32_t ix0, iy0, nx, ny; } gbp_rect; /* cells [ix0, ix0+nx) x [iy0, iy0+ny); NULL = whole map */
+#define GBP_SRC_F64_XMAJOR  0  /* double src[i*ld + j] = z[ix0+i][iy0+j], ld >= rect.ny */
+#define GBP_SRC_F32_GRIDMAP 1  /* a whole grid_map layer as it lies in memory: float,
+                                  column-major, start index 0, ld >= terrain nx;
+                                  z[ix][iy] = src[(NX-1-ix) + (NY-1-iy)*ld]
+                                  (fast_terrain_map.cpp:57-61); the rect selects which
+                                  cells are taken */
+/* z, and dx / dy / dz (all three or none), in src_layout with leading dimension
+ * ld.  Slope layers given for a handle created without them: GBP_E_INVALID_ARG;
+ * omitted for a handle that has them: they stay as they are.  A rectangle that
+ * is empty or leaves the map, or an ld below the layout's minimum: GBP_E_SHAPE;
+ * an unknown layout: GBP_E_INVALID_ARG.
+ * All or nothing: an fp32-storage handle holds only heights that round-trip
+ * through float, and an update keeps that true.  An fp64 source height that is
+ * neither NaN nor float-representable rejects the whole update, slope layers
+ * included, and nothing is written.  gbp_terrain_update_host finds that on the
+ * host before it stages anything and returns GBP_E_UNSUPPORTED.
+ * gbp_terrain_update_dev cannot: its first launch checks the patch and writes
+ * status[0] (device, one word: 0 applied, 1 rejected), its second applies the
+ * patch unless it reads 1; the call itself returns GBP_OK.  A GBP_SRC_F32_GRIDMAP
+ * source and an fp64-storage handle cannot be rejected (status[0] = 0; status
+ * may then be NULL).  NaN heights are stored as NaN.
+ * Ordering: gbp_terrain_update_dev takes DEVICE pointers and only enqueues on
+ * `stream`, like every _dev entry: work enqueued on that stream before it sees
+ * the old map, work enqueued after it the new one.  Ordering against work on
+ * any other stream (the handle's own host stream of the _host entries
+ * included) is the caller's.  gbp_terrain_update_host takes host pointers, runs
+ * on the handle's host stream after every earlier gbp_terrain_update_dev, and
+ * returns when the device and the host copy hold the patch. */
+int gbp_terrain_update_dev(gbp_terrain *t, const gbp_rect *r, int src_layout, int64_t ld,
+                           const void *z, const void *dx, const void *dy, const void *dz,
+                           int32_t *status, gbp_stream stream);
+int gbp_terrain_update_host(gbp_terrain *t, const gbp_rect *r, int src_layout, int64_t ld,
+                            const void *z, const void *dx, const void *dy, const void *dz);
+/* The heights the device holds, x-major z[r.nx][r.ny] (host, synchronous, after
+ * every earlier gbp_terrain_update_dev).  A height lies in up to two places
+ * (slot 0 of x-pair ix, slot 1 of x-pair ix-1): copy 0 reads row ix from slot 0
+ * of pair ix (row nx-1, which has none, from slot 1 of pair nx-2), copy 1 reads
+ * row ix from slot 1 of pair ix-1 (row 0 from slot 0 of pair 0). */
+int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z);
+
 /* engine options (per handle) */
 #define GBP_OPT_KERNEL        1  /* GBP_KERNEL_* for the validate/extend entry points */
 #define GBP_OPT_BLOCK         2  /* threads per workgroup (multiple of 64, <= 512; the

@@ -19,6 +19,7 @@
 #include <stdexcept>
 #include <type_traits>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <utility>
 #include <vector>
@@ -131,6 +132,27 @@ class FastTerrainMap {
   // the node's map_data_source "csv" path without ROS (terrainArraysFromCSV)
   void loadMapFromCSV(const std::string &dir);
 
+  // New heights for the loaded map, in place (gbp_terrain_update_host): the
+  // engine handle, its options, sampling configuration and workspaces and the
+  // planner workspaces created for it stay; the geometry and the storage type
+  // do not change (heights an fp32 handle cannot hold throw).  Cells [ix0, ix0 +
+  // pnx) x [iy0, iy0 + pny), flat x-major z[i * pny + j]; dx/dy/dz all three or
+  // null (null: the handle's slope layers stay as they are).
+  void updateDataFlat(int ix0, int iy0, int pnx, int pny, const double *z, const double *dx,
+                      const double *dy, const double *dz);
+  // the whole map from x-major nested vectors (slope layers when all three
+  // have x_size rows, as loadData)
+  void updateData(const std::vector<std::vector<double>> &z_data,
+                  const std::vector<std::vector<double>> &dx_data,
+                  const std::vector<std::vector<double>> &dy_data,
+                  const std::vector<std::vector<double>> &dz_data);
+  // terrainMapCallback (global_body_planner.cpp:37-44) on a map that keeps its
+  // geometry: when the map's size, every x / y position and the presence of
+  // slope layers equal the loaded map's bit for bit, the heights are updated
+  // in place and true is returned; otherwise loadDataFromGridMap(map), false.
+  template <class GridMap>
+  bool updateFromGridMap(const GridMap &map);
+
   double getGroundHeight(const double x, const double y);               // :94-132
   bool heightIsNan(const double x, const double y);                     // :135-157
   std::array<double, 3> getSurfaceNormal(const double x, const double y);  // :160-213
@@ -148,6 +170,7 @@ class FastTerrainMap {
   int device_;
   gbp_terrain *handle_ = nullptr;
   bool owned_ = true;
+  bool slopes_ = false;  // the handle was loaded with slope layers
   int x_size_ = 0, y_size_ = 0;
   std::vector<double> x_data_, y_data_;
 };
@@ -709,6 +732,55 @@ void FastTerrainMap::loadDataFromGridMap(const GridMap &map) {
     }
   loadDataFlat(x_size, y_size, x.data(), y.data(), z.data(), slopes ? dx.data() : nullptr,
                slopes ? dy.data() : nullptr, slopes ? dz.data() : nullptr);
+}
+
+template <class GridMap>
+bool FastTerrainMap::updateFromGridMap(const GridMap &map) {
+  using Index = typename std::decay<decltype(map.getStartIndex())>::type;
+  using Position = typename std::decay<decltype(map.getPosition())>::type;
+  const int x_size = map.getSize()(0);
+  const int y_size = map.getSize()(1);
+  const bool slopes = map.exists("dx");
+  bool same = handle_ && owned_ && x_size == x_size_ && y_size == y_size_ && slopes == slopes_ &&
+              x_data_.size() == (size_t)x_size && y_data_.size() == (size_t)y_size;
+  for (int i = 0; same && i < x_size; i++) {
+    Index index((x_size - 1) - i, 0);
+    Position position;
+    map.getPosition(index, position);
+    const double v = position.x();
+    same = std::memcmp(&v, &x_data_[i], sizeof v) == 0;
+  }
+  for (int i = 0; same && i < y_size; i++) {
+    Index index(0, (y_size - 1) - i);
+    Position position;
+    map.getPosition(index, position);
+    const double v = position.y();
+    same = std::memcmp(&v, &y_data_[i], sizeof v) == 0;
+  }
+  if (!same) {
+    loadDataFromGridMap(map);
+    return false;
+  }
+  std::vector<double> z((size_t)x_size * y_size), dx, dy, dz;
+  if (slopes) {
+    dx.resize(z.size());
+    dy.resize(z.size());
+    dz.resize(z.size());
+  }
+  for (int i = 0; i < x_size; i++)
+    for (int j = 0; j < y_size; j++) {
+      Index index((x_size - 1) - i, (y_size - 1) - j);
+      const size_t k = (size_t)i * y_size + j;
+      z[k] = (double)map.at("elevation", index);
+      if (slopes) {
+        dx[k] = (double)map.at("dx", index);
+        dy[k] = (double)map.at("dy", index);
+        dz[k] = (double)map.at("dz", index);
+      }
+    }
+  updateDataFlat(0, 0, x_size, y_size, z.data(), slopes ? dx.data() : nullptr,
+                 slopes ? dy.data() : nullptr, slopes ? dz.data() : nullptr);
+  return true;
 }
 
 }  // namespace gbp_amd
