@@ -206,59 +206,42 @@ constexpr int LP_N = 14;  // values per wave
 __device__ unsigned long long gbp_loop_prof[8192 * LP_N];
 #define LP_T(v) const unsigned long long v = __builtin_readcyclecounter()
 #define LP_ADD(k, a, b) lp[k] += (b) - (a)
+#define LP_DO(x) x
 #else
 #define LP_T(v)
 #define LP_ADD(k, a, b)
+#define LP_DO(x)
 #endif
 
-// The refill's prefetch window: each wave owns 64 + pf
-// row slots.  A lane's attempt lives in the slot `row` of its wave; the pf
-// slots no lane holds form a queue (LDS, always full): its first `staged`
-// entries hold the attempts cur .. cur + staged - 1, loaded a step ahead by
-// LDS-direct loads that nothing waits for until the next refill, the rest are
-// free.  A refill hands the staged slots to the idle lanes in rank order (the
-// lane's old slot takes the queue entry's place: popping the head and pushing
-// the tail of a full queue meet in one cell), so no row is copied.
-// Built only with -DGBP_REFILL_WINDOW (A/B): measured slower than the direct
-// refill, which is the default: no window (pf = 0), every
-// refill loads its rows itself, dir issued with the rows.
-[[maybe_unused]] constexpr int PF_MAX = 32;
-
-// LDS bytes behind the coordinate vectors: rows, s_new rings, the window's queue
-inline size_t rows_bytes(int block, int pf) {
+// LDS bytes behind the coordinate vectors: the attempt rows and the s_new rings
+inline size_t rows_bytes(int block) {
   const size_t nwv = (size_t)(block / WAVE);
-  return sizeof(double) * SA_ROW * (size_t)(WAVE + pf) * nwv + sizeof(SnewRec) * SN_RING * nwv +
-         sizeof(int) * ((nwv * (size_t)pf + 1) & ~(size_t)1);
+  return sizeof(double) * SA_ROW * (size_t)WAVE * nwv + sizeof(SnewRec) * SN_RING * nwv;
 }
 
-// one attempt row (S 64 B, A 80 B, dir in the 19th double's low word) from
-// global memory straight into the LDS row at `row` (wave-uniform): lanes
-// 0..35 one dword each, lane 36 the dir byte.  The loads are not in the
-// compiler's count: the consumer waits vmcnt(0) itself (loads return in
-// order, so the compiler's own counted waits only get stricter).
-__device__ __forceinline__ void row_to_lds(const double *S, const double *A, const uint8_t *dir,
-                                           unsigned int i, double *row, int lane) {
-  const unsigned int lds = __builtin_amdgcn_readfirstlane(
-      (unsigned int)(uintptr_t)(__attribute__((address_space(3))) void *)row);
-  const uint32_t *src = lane < 16 ? (const uint32_t *)(S + 8 * (size_t)i) + lane
-                                  : (const uint32_t *)(A + 10 * (size_t)i) + (lane - 16);
-  unsigned int keep;
-  if (lane < 36)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds) : "memory");
-  if (dir && lane == 36)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                 "global_load_lds_ubyte %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(dir + i), "s"(lds) : "memory");
-}
+// The refill's register ring.  A wave's slice is
+// contiguous and handed out in order, so the rows it needs next are known
+// ahead.  Number the slice k = i - begin: lane l keeps the row with
+// k = l (mod 64) that has not been handed out yet in registers (18 doubles and
+// dir), loaded a step ahead by loads nothing waits for; at a refill the
+// holders write their rows into the idle lanes' LDS rows.  Compiled in where
+// its 38 registers fit the budget of 2 waves per SIMD (256 VGPRs) with room to
+// spare and no scratch (make resource-usage): fp32 heights at 182-188 VGPRs
+// before the ring.  Not at W = 3 / 4 (168 / 128 VGPRs), not with fp64 heights
+// (223-229 before the ring), not for the straight-line bracket on coordinates
+// from global memory (214): with the ring those come out at exactly 256, two
+// of them with scratch.  RING, the kernel's last template argument, is this
+// and the launch's choice: launch_validate_w takes the ring's kernel only for
+// batches that give some wave more than 64 attempts.
+template <class ZT, int W, int CM, bool ONE>
+constexpr bool refill_ring = W <= 2 && sizeof(ZT) == 4 && !(CM == 0 && ONE);
 
-template <class ZT, bool ADAPTIVE, int W, int CM, bool ONE>
+template <class ZT, bool ADAPTIVE, int W, int CM, bool ONE, bool RING>
 __global__ __launch_bounds__(512, W) void k_validate_persistent(
     TerrainView<ZT> T0, int n, const double *__restrict__ S, const double *__restrict__ A,
     const uint8_t *__restrict__ dir, int dir_all, uint8_t *__restrict__ valid,
     double *__restrict__ s_new, double *__restrict__ t_new, uint32_t *__restrict__ flags,
-    uint32_t *__restrict__ counts, const int *__restrict__ n_dev, int helpers, int xcd_map, int pf) {
+    uint32_t *__restrict__ counts, const int *__restrict__ n_dev, int helpers, int xcd_map) {
 #ifdef GBP_LOOP_PROF
   const unsigned long long lp_entry = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -268,9 +251,8 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
   // (wave-uniform values the compiler cannot prove uniform: kept in scalar registers)
   const int nwv = blockDim.x / WAVE, wv = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE);
   double *const SA = gbp_smem + (CM == 1 ? (T0.nx + T0.ny + 1) & ~1 : 0);  // attempt rows
-  double *const wave_rows = SA + (size_t)wv * (WAVE + pf) * SA_ROW;
-  SnewRec *const ring = (SnewRec *)(SA + (size_t)nwv * (WAVE + pf) * SA_ROW) + wv * SN_RING;
-  [[maybe_unused]] int *const Q = (int *)(ring + (nwv - wv) * SN_RING) + wv * pf;  // the window's slot queue
+  double *const wave_rows = SA + (size_t)wv * WAVE * SA_ROW;
+  SnewRec *const ring = (SnewRec *)(SA + (size_t)nwv * WAVE * SA_ROW) + wv * SN_RING;
   // work source: a fixed contiguous slice [cur, end) per wave, handed out to
   // the wave's idle lanes in order (no atomics).  Dynamic dequeues (one or
   // eight device-scope heads, chunked, per-workgroup LDS queues; round 4: the
@@ -298,15 +280,16 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
 #pragma unroll
     for (int k = 0; k < 10; k++) r[8 + k] = A[10 * (size_t)i + k];
   };
-#ifdef GBP_REFILL_WINDOW
-  // the wave's first rows, fetched (cold) ahead of the coordinate staging
-  // (without the window too this measured slower than filling in the loop's
-  // first refill: DESIGN section 5.1, profiles/wg_handover_ab.txt)
-  const unsigned int take0 = min(end - cur, (unsigned int)WAVE);
-  double row0[18];
-  int dir0 = dir_all;
-  if ((unsigned int)lane < take0) load_row(cur + lane, row0, dir0);
-#endif
+  // the ring: row `nk` of the slice (counted from `begin`) in pr / pd while
+  // `held`.  The first 64 rows are not the ring's: the idle lanes load them
+  // themselves in the loop's first refill (issued ahead of the coordinate
+  // staging they measured slower: DESIGN section 5.1, profiles/wg_handover_ab.txt)
+  const unsigned int begin = cur;
+  [[maybe_unused]] double pr[18];
+  [[maybe_unused]] int pd = dir_all;
+  [[maybe_unused]] unsigned int nk = WAVE + lane;
+  [[maybe_unused]] bool held = false;
+  bool pend = false;  // this lane decided its attempt in the last step: outputs not stored yet
   const TerrainView<ZT> T = CM == 1 ? stage_coords(T0, gbp_smem) : T0;
   int ring_n = 0;  // wave-uniform
   // s_new of the ring's first cnt entries, one per lane (converged)
@@ -329,8 +312,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     }
   };
   Lane L;
-  int row = lane;  // this lane's row slot among its wave's 64 + pf
-  L.s = wave_rows + row * SA_ROW;
+  L.s = wave_rows + lane * SA_ROW;
   L.a = L.s + 8;
   L.stage = ST_IDLE;
   // a fresh attempt i of direction d in the lane's row
@@ -342,79 +324,99 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     L.tnew_set = 0;
     enter_stage(L, d == GBP_FORWARD ? ST_FWD_STANCE : ST_REV_FLIGHT);
   };
-#ifdef GBP_REFILL_WINDOW
-  unsigned int staged = 0, qh = 0;  // the queue's staged entries and its head (wave-uniform)
-  if (lane < pf) Q[lane] = WAVE + lane;
-  if ((unsigned int)lane < take0) {
-#pragma unroll
-    for (int k = 0; k < 18; k++) L.s[k] = row0[k];
-    start(cur + lane, dir0);
-  }
-  cur += take0;
-#endif
 #ifdef GBP_LOOP_PROF
   unsigned long long lp[LP_N] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   lp[12] = lp_entry;  // the wave's entry; lp[13]: its first sample (staging and first fill done)
   lp[8] = __builtin_amdgcn_s_memrealtime();
   LP_T(lp_start);
+  unsigned long long lp_out = 0;  // the outputs' cycles inside the refill's span
 #endif
+  // valid, t_new, flags and counts of the attempts the last step decided
+  // (`pend`), and their s_new queue entries, from the lane state
+  auto put_outputs = [&]() {
+    LP_T(t0o);
+    const bool queue = pend && s_new && L.snew_kind != SN_NONE;
+    if (pend) {
+      const size_t i = (size_t)L.idx;
+      uint32_t f = L.f | L.acc.flags;
+      if (L.snew_kind != SN_NONE) f |= GBP_F_SNEW_SET;
+      if (L.tnew_set) f |= GBP_F_TNEW_SET;
+      if (valid) valid[i] = (f & GBP_F_VALID) ? 1 : 0;
+      if (t_new && L.tnew_set) t_new[i] = L.tnew;
+      flags[i] = f;
+      if (counts) counts[i] = (L.acc.G & 0xFFFFu) | (L.acc.V << 16);
+    }
+    pend = false;
+    const unsigned long long qm = __ballot(queue);
+    if (qm) {
+      if (queue) ring[ring_n + __popcll(qm & lt_mask)] = SnewRec{L.idx, L.snew_kind, L.snew_p};
+      ring_n += __popcll(qm);
+      if (ring_n >= WAVE) {
+        flush(WAVE);
+        ring_n -= WAVE;
+        SnewRec r;
+        if (lane < ring_n) r = ring[WAVE + lane];
+        if (lane < ring_n) ring[lane] = r;
+      }
+    }
+    LP_T(t1o);
+    LP_ADD(4, t0o, t1o);
+    LP_DO(lp_out = t1o - t0o);
+  };
   for (;;) {
     LP_T(t0);
     const bool need = L.stage == ST_IDLE;
-    unsigned long long m = __ballot(need);
-    if (m && cur < end) {
-      const unsigned int take = min(end - cur, (unsigned int)__popcll(m));
-      const unsigned int rank = (unsigned int)__popcll(m & lt_mask);
-      const bool mine = need && rank < take;
-      unsigned int ts = 0;
-#ifdef GBP_REFILL_WINDOW
-      // the first `ts` of them from the window: a slot swap, no copy
-      ts = min(take, staged);
-      if (ts) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the window's loads, issued a step ago
-        if (mine && rank < ts) {
-          unsigned int p = qh + rank;
-          p -= p >= (unsigned int)pf ? (unsigned int)pf : 0u;
-          const int got = Q[p];
-          Q[p] = row;  // the slot given up is free window space
-          row = got;
-          L.s = wave_rows + row * SA_ROW;
-          L.a = L.s + 8;
-          start(cur + rank, dir ? ((const int *)L.s)[36] & 0xFF : dir_all);
-        }
-        qh += ts;
-        qh -= qh >= (unsigned int)pf ? (unsigned int)pf : 0u;
-        staged -= ts;
-      }
-#endif
-      if (mine && rank >= ts) {  // the rest, and every refill of a build without the window
-        double r[18];
-        int d = dir_all;
-        load_row(cur + rank, r, d);
+    const unsigned long long m = __ballot(need);
+    const unsigned int take = min(end - cur, (unsigned int)__popcll(m));  // 0: nothing idle, or the slice is out
+    const unsigned int rank = (unsigned int)__popcll(m & lt_mask);
+    const bool mine = need && rank < take;
+    // Past the first fill every row of [cur, cur + 64) inside the slice is in
+    // the ring: a holder is emptied only here and loads its next row in the
+    // same step, and take <= 64.
+    const bool from_ring = RING && take && cur != begin;
+    if (from_ring) {
+      // holder of the r-th row handed out -> the LDS row of the idle lane of
+      // rank r; dir travels in the low word of the row's 19th double
+      // (the idle lane of rank r pushes its number to the holder of row
+      // cur + r, lane (cur - begin + r) mod 64; the other lanes push to the
+      // holder of row cur + take, which hands nothing out, or, at take = 64,
+      // are not there)
+      const unsigned int r = nk - (cur - begin);
+      const int dest = __builtin_amdgcn_ds_permute((int)((cur - begin + (mine ? rank : take)) & 63u) << 2, lane);
+      if (held && r < take) {
+        double *const dst = wave_rows + dest * SA_ROW;
 #pragma unroll
-        for (int k = 0; k < 18; k++) L.s[k] = r[k];
-        start(cur + rank, d);
+        for (int k = 0; k < 18; k++) dst[k] = pr[k];
+        if (dir) ((int *)dst)[36] = pd;
+        held = false;
+        nk += WAVE;
       }
-      cur += take;
+      // a wave's LDS operations are in order; the compiler must keep the
+      // idle lanes' reads below the holders' writes
+      asm volatile("" ::: "memory");
     }
-#ifdef GBP_REFILL_WINDOW
-    // top the window up to the slice's next pf attempts: the loads land during
-    // this step's state check; nothing waits for them before the next refill
-    if (pf && min(end - cur, (unsigned int)pf) > staged) {
-      const unsigned int want = min(end - cur, (unsigned int)pf);
-      const int qv = Q[lane < pf ? lane : 0];
-      for (unsigned int k = staged; k < want; k++) {
-        unsigned int p = qh + k;
-        p -= p >= (unsigned int)pf ? (unsigned int)pf : 0u;
-        row_to_lds(S, A, dir, cur + k, wave_rows + __builtin_amdgcn_readlane(qv, p) * SA_ROW, lane);
-      }
-      staged = want;
+    // A kernel with the ring writes the last step's outputs here, behind the
+    // holders' wait and ahead of start() (which replaces the lane state they
+    // are read from), not where the attempts were decided: loads and stores
+    // share one counter, so that wait (for rows loaded a step ago) would also
+    // cover stores issued just ahead of it.
+    if (RING) put_outputs();
+    if (from_ring) {
+      if (mine) start(cur + rank, dir ? ((const int *)L.s)[36] & 0xFF : dir_all);
+    } else if (mine) {  // the first fill, and every refill of a kernel without the ring
+      double r[18];
+      int d = dir_all;
+      load_row(cur + rank, r, d);
+#pragma unroll
+      for (int k = 0; k < 18; k++) L.s[k] = r[k];
+      start(cur + rank, d);
     }
-#endif
+    cur += take;
     const unsigned long long act = __ballot(L.stage != ST_IDLE);
     if (!act) break;
     LP_T(t1);
     LP_ADD(0, t0, t1);
+    LP_DO(if (RING) lp[0] -= lp_out; lp_out = 0);  // (the outputs keep their own slot in the profile)
 #ifdef GBP_LOOP_PROF
     if (!lp[7]) lp[13] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -440,7 +442,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
       const int j = __popcll(idle & lt_mask);
       const int src = owner ? lane : nth_set_bit(act, j % n_act);
       slot = owner ? 0 : 1 + j / n_act;
-      ps = wave_rows + __shfl(row, src) * SA_ROW;  // the owner's attempt row
+      ps = wave_rows + src * SA_ROW;  // the owner's attempt row
       st = __shfl(L.stage, src);
       double t = __shfl(L.t, src), ts = __shfl(L.ts, src);
       vbase = __shfl(L.acc.V, src);
@@ -463,6 +465,24 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     }
     LP_T(t3);
     LP_ADD(2, t2, t3);
+    // The ring's loads: every lane whose entry is empty and whose next row is
+    // inside the slice.  Here, behind the state check's gathers: loads return
+    // in order under one counter, so issued ahead of the gathers their first
+    // counted wait would cover this round trip.  The next to wait is the next
+    // step's refill or its gathers; the first burst leaves after step 1's
+    // state check, clear of every wave's first fill.
+    // dir goes last: the row loads' address arithmetic reuses dead ring
+    // registers, whose counted waits (against the last burst) would otherwise
+    // also cover a dir byte issued a few instructions earlier.
+    if (RING && !held && nk < end - begin) {
+      const size_t i = begin + nk;
+#pragma unroll
+      for (int k = 0; k < 8; k++) pr[k] = S[8 * i + k];
+#pragma unroll
+      for (int k = 0; k < 10; k++) pr[8 + k] = A[10 * i + k];
+      if (dir) pd = dir[i];
+      held = true;
+    }
     bool decided = false;
     if (owner) {  // the lane's own sample
       L.acc.G += acc_s.G;
@@ -510,32 +530,9 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
     lp[7] += 1;
 #endif
     const bool fin = owner && decided;
-    const bool queue = fin && s_new && L.snew_kind != SN_NONE;
-    if (fin) {
-      const size_t i = (size_t)L.idx;
-      uint32_t f = L.f | L.acc.flags;
-      if (L.snew_kind != SN_NONE) f |= GBP_F_SNEW_SET;
-      if (L.tnew_set) f |= GBP_F_TNEW_SET;
-      if (valid) valid[i] = (f & GBP_F_VALID) ? 1 : 0;
-      if (t_new && L.tnew_set) t_new[i] = L.tnew;
-      flags[i] = f;
-      if (counts) counts[i] = (L.acc.G & 0xFFFFu) | (L.acc.V << 16);
-    }
-    const unsigned long long qm = __ballot(queue);
-    if (qm) {
-      if (queue) ring[ring_n + __popcll(qm & lt_mask)] = SnewRec{L.idx, L.snew_kind, L.snew_p};
-      ring_n += __popcll(qm);
-      if (ring_n >= WAVE) {
-        flush(WAVE);
-        ring_n -= WAVE;
-        SnewRec r;
-        if (lane < ring_n) r = ring[WAVE + lane];
-        if (lane < ring_n) ring[lane] = r;
-      }
-    }
+    pend = fin;  // with the ring the outputs wait for the top of the next step
+    if (!RING) put_outputs();
     if (fin) L.stage = ST_IDLE;
-    LP_T(t5);
-    LP_ADD(4, t4, t5);
   }
   if (ring_n) flush(ring_n);
 #ifdef GBP_LOOP_PROF
@@ -949,7 +946,7 @@ int coord_mode(const gbp_terrain *t, bool lds_ok) {
 }
 
 // Workgroup size of the validate launches: the one place it is chosen (the
-// coordinate mode, the window, the LDS request and the grid all size from it).
+// coordinate mode, the LDS request and the grid all size from it).
 // GBP_OPT_BLOCK, once set, is used as given.  Unset (0), the persistent kernel
 // runs 128 lanes where opt_waves * 2 such workgroups, each with its staged
 // coordinate vectors, fit a CU's 160 KB: the same waves per CU and the same
@@ -958,7 +955,7 @@ int coord_mode(const gbp_terrain *t, bool lds_ok) {
 // do the direct kernel and the planner loop's launches (n_dev).
 int validate_block(const gbp_terrain *t, bool n_dev) {
   if (t->opt_block) return (int)t->opt_block;
-  const size_t wg = stage_bytes(t->nx, t->ny) + rows_bytes(128, 0);
+  const size_t wg = stage_bytes(t->nx, t->ny) + rows_bytes(128);
   if (!n_dev && (size_t)t->opt_waves * 2 * wg <= 160 * 1024) return 128;
   return 256;
 }
@@ -970,7 +967,7 @@ int validate_coord_mode(const gbp_terrain *t, bool direct, bool n_dev = false) {
   // the attempt rows and s_new rings are the persistent kernel's alone
   // (launch_validate_w allocates neither for the direct kernel)
   const int block = validate_block(t, n_dev);
-  const size_t rows = direct ? 0 : rows_bytes(block, 0);
+  const size_t rows = direct ? 0 : rows_bytes(block);
   const size_t per_cu = std::max<int64_t>(1, t->opt_waves * 256 / block) *
                         (stage_bytes(t->nx, t->ny) + rows);
   const bool lds_ok = t->opt_lds_coords && stage_bytes(t->nx, t->ny) + rows <= t->lds_max &&
@@ -980,24 +977,6 @@ int validate_coord_mode(const gbp_terrain *t, bool direct, bool n_dev = false) {
   // on both axes reads its vectors from global memory (general search)
   if (!direct && !(t->one_x && t->one_y)) return 0;
   return coord_mode(t, lds_ok);
-}
-
-// rows of the refill's prefetch window per wave (k_validate_persistent): as
-// many of PF_MAX as fit behind the coordinate vectors and the 64 rows, both in
-// a workgroup's limit and among the workgroups that share a CU's 160 KB; 0
-// (every refill loads its rows itself) when nothing fits.  The coordinate mode
-// is chosen first (validate_coord_mode) and never gives way to the window.
-int refill_window(const gbp_terrain *t, size_t coords, bool n_dev = false) {
-#ifndef GBP_REFILL_WINDOW
-  return 0;  // the default build has no window
-#else
-  const int block = validate_block(t, n_dev);
-  const size_t wgs = (size_t)std::max<int64_t>(1, t->opt_waves * 256 / block);
-  const size_t cap = std::min<size_t>(t->lds_max, 160 * 1024 / wgs);
-  for (int pf = PF_MAX; pf > 0; pf--)
-    if (coords + rows_bytes(block, pf) <= cap) return pf;
-  return 0;
-#endif
 }
 
 template <class ZT, bool AD, int W, int CM, bool ONE>
@@ -1033,10 +1012,18 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
       // waves starting with idle lanes that help from the first step
       // (65,536 attempts: 0.084 -> 0.072 ms; 262,144: unchanged)
       const int64_t g = std::max<int64_t>(1, std::min<int64_t>(resident, (m + WAVE - 1) / WAVE));
-      const int pf = refill_window(t, coords, n_dev != nullptr);
-      hipLaunchKernelGGL((k_validate_persistent<ZT, AD, W, CM, ONE>), dim3((unsigned)g), dim3(block),
-                         coords + rows_bytes(block, pf), st, T, (int)m, s + 8 * off, a + 10 * off, d, dir_all,
-                         v, sn, tn, flags + off, c, n_dev, (int)t->opt_helpers, (int)t->opt_xcd_map, pf);
+      // the ring's kernel only where a slice outruns the first fill (more than
+      // 64 attempts for some wave): below that it would carry the ring's
+      // registers for nothing (config 2 measured 1.5-3 % slower with them)
+      constexpr bool CAN = refill_ring<ZT, W, CM, ONE>;
+      const bool ring = CAN && m > (int64_t)WAVE * g * (block / WAVE);
+      auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)g), dim3(block), coords + rows_bytes(block), st, T, (int)m,
+                           s + 8 * off, a + 10 * off, d, dir_all, v, sn, tn, flags + off, c, n_dev,
+                           (int)t->opt_helpers, (int)t->opt_xcd_map);
+      };
+      if (ring) go(k_validate_persistent<ZT, AD, W, CM, ONE, CAN>);
+      else go(k_validate_persistent<ZT, AD, W, CM, ONE, false>);
     }
     HIPCHK(hipGetLastError());
   }
@@ -1213,10 +1200,9 @@ int gbp_validate_lds_plan(int nx, int ny, int64_t block, int64_t waves, size_t l
   t.lds_max = lds_max;
   const int cm = validate_coord_mode(&t, false);
   const size_t coords = cm == 1 ? stage_bytes(nx, ny) : 0;
-  const int pf = refill_window(&t, coords);
   if (coord_lds) *coord_lds = cm == 1;
-  if (window) *window = pf;
-  if (bytes) *bytes = coords + rows_bytes(validate_block(&t, false), pf);
+  if (window) *window = 0;  // the LDS prefetch window is retired
+  if (bytes) *bytes = coords + rows_bytes(validate_block(&t, false));
   return GBP_OK;
 }
 
@@ -1469,9 +1455,7 @@ int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value) {
     case GBP_OPT_COORD_MODE:  // what the validate kernel of the current options uses
       *value = validate_coord_mode(t, t->opt_kernel == GBP_KERNEL_DIRECT);
       return GBP_OK;
-    case GBP_OPT_REFILL_WINDOW:  // the persistent kernel's, at the current options
-      *value = refill_window(t, validate_coord_mode(t, false) == 1 ? stage_bytes(t->nx, t->ny) : 0);
-      return GBP_OK;
+    case GBP_OPT_REFILL_WINDOW: *value = 0; return GBP_OK;  // retired with the LDS window: reads 0
     default: return GBP_E_INVALID_ARG;
   }
 }

@@ -213,9 +213,9 @@ int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z
                                     persistent validate launch at the current options:
                                     GBP_OPT_BLOCK where the caller set it, else 128 or
                                     256 by the rule above                              */
-#define GBP_OPT_REFILL_WINDOW 19 /* read-only: rows per wave of the persistent validate
-                                    kernel's prefetch window at the current options
-                                    (0: every refill loads its rows itself)           */
+#define GBP_OPT_REFILL_WINDOW 19 /* read-only, always 0: the persistent validate kernel's
+                                    LDS prefetch window is retired; rows are
+                                    prefetched into registers where they fit            */
 #define GBP_KERNEL_DIRECT     0  /* one lane per attempt                              */
 #define GBP_KERNEL_PERSISTENT 1  /* persistent waves, lanes re-packed per sample      */
 int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value);
@@ -224,8 +224,8 @@ int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value);
  * with straight-line brackets (no device needed): `block` threads per
  * workgroup (0: GBP_OPT_BLOCK not set, the launch's own choice), `waves` per SIMD, `lds_max` bytes a workgroup may use.  Outputs
  * (each may be NULL): coord_lds 1 when the coordinate vectors are staged in
- * LDS, window the rows per wave of the refill's prefetch window (0: every
- * refill loads its rows itself), bytes the dynamic LDS of the launch. */
+ * LDS, window 0 (the refill's LDS prefetch window is retired; the argument
+ * stays for callers), bytes the dynamic LDS of the launch. */
 int gbp_validate_lds_plan(int nx, int ny, int64_t block, int64_t waves, size_t lds_max,
                           int *coord_lds, int *window, size_t *bytes);
 
