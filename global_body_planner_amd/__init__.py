@@ -16,13 +16,13 @@ from ._lib import (ADVANCED, FLIGHT, FORWARD, REACHED, REVERSE, STANCE, TRAPPED,
 from .terrain_data import TerrainData, csv_gridmap, csv_direct, synth_rough, synth_fractal
 from .engine import (Terrain, PairResult, ExtendResult, DeviceTree, PlanWorkspace, nearest,
                      neighbors, knn, knn_yaw, device_count)
-from .planner import revalidate_trees
+from .planner import revalidate_trees, reroot_tree
 
 __all__ = [
     "ADVANCED", "FLIGHT", "FORWARD", "REACHED", "REVERSE", "STANCE", "TRAPPED", "GbpError",
     "KERNEL_DIRECT", "KERNEL_PERSISTENT", "TerrainData", "csv_gridmap", "csv_direct",
     "synth_rough", "synth_fractal", "Terrain", "PairResult", "ExtendResult", "DeviceTree",
     "PlanWorkspace", "nearest", "neighbors", "knn", "knn_yaw", "device_count",
-    "revalidate_trees",
+    "revalidate_trees", "reroot_tree",
 ]
 __version__ = "0.2.0"

@@ -57,7 +57,8 @@ EXPORTS = [
     "gbp_tree_size", "gbp_tree_read", "gbp_tree_append_host", "gbp_tree_load_host",
     "gbp_tree_device_ptrs", "gbp_vertex_map_order", "gbp_vertex_map_rank",
     "gbp_tree_revalidate_dev", "gbp_tree_prune_dev", "gbp_tree_revalidate_host",
-    "gbp_tree_read_links",
+    "gbp_tree_read_links", "gbp_tree_reroot_dev", "gbp_tree_reroot_host",
+    "gbp_tree_reroot_last",
     "gbp_plan_ws_create", "gbp_plan_ws_destroy", "gbp_plan_reset", "gbp_plan_half_dev",
     "gbp_plan_halves_dev", "gbp_plan_star_config", "gbp_plan_stage_timing", "gbp_plan_stage_times",
     "gbp_plan_status_read", "gbp_plan_resolve_host", "gbp_extend_tree_dev",
@@ -83,6 +84,14 @@ class PruneStats(ctypes.Structure):
     """gbp_prune_stats (include/gbp.h): what a prune kept and why the rest went."""
     _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
                 ("n_edge_invalid", ctypes.c_int64), ("n_inherited", ctypes.c_int64)]
+
+
+class RerootStats(ctypes.Structure):
+    """gbp_reroot_stats (include/gbp.h): what a re-root kept, why the rest went,
+    and the depth of the kept tree."""
+    _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
+                ("n_outside", ctypes.c_int64), ("n_edge_invalid", ctypes.c_int64),
+                ("n_inherited", ctypes.c_int64), ("depth", ctypes.c_int64)]
 
 
 def sampling(state_flag=False, state_p=0.05, speed_direction=False, action_flag=False,
@@ -176,6 +185,9 @@ def load(path=None):
         "gbp_tree_revalidate_dev": (I, [P, P, I64, I, I, P, P, P]),
         "gbp_tree_prune_dev": (I, [P, I64, P, P, P, P]),
         "gbp_tree_revalidate_host": (I, [P, P, I, I, P, P, P]),
+        "gbp_tree_reroot_dev": (I, [P, I64, ctypes.c_int32, P, P, P, P]),
+        "gbp_tree_reroot_host": (I, [P, P, ctypes.c_int32, I, I, P, P, P]),
+        "gbp_tree_reroot_last": (I, [P, P]),
         "gbp_plan_ws_create": (I, [P, I64, P]),
         "gbp_plan_ws_destroy": (I, [P]),
         "gbp_plan_reset": (I, [P, I64, P]),

@@ -53,6 +53,13 @@
 // hold, k_prune_count / k_prune_scan / k_prune_rank number them in order and
 // k_prune_move_rows / k_prune_move_links move them into fresh arrays.
 //
+// A tree re-rooted at one of its vertices (gbp_tree_reroot_dev): the same
+// jumping with the new root as a second terminal and the depth below it summed
+// along (k_reroot_seed / k_reroot_jump), the compaction with the new root
+// placed first (k_reroot_count / k_reroot_scan / k_reroot_rank), the prune's
+// move, then g derived again level by level (k_reroot_levels / k_reroot_order
+// sort the vertices by depth, k_reroot_g_wide / k_reroot_g_narrow write g).
+//
 // FRAGILE decisions (gbp.h) stop the sequence at the next gate: the kernel
 // that meets one sets status.halt; every later kernel of the group returns at
 // once; the host re-decides the flagged items with glibc
@@ -2799,6 +2806,246 @@ __global__ __launch_bounds__(TB) void k_prune_move_links(gbp_tree o, gbp_tree f,
   }
 }
 
+// ============================================================================
+// re-rooting a tree at one of its vertices (gbp_tree_reroot_dev)
+// ============================================================================
+// The keep rule is the prune's word scheme with two terminals: the new root k
+// is its own ancestor and never dead, the old root is its own ancestor and
+// dead.  After the rounds a vertex's ancestor is k exactly when it lies below
+// k, and its dead bit then tells whether an edge between the two failed.  A
+// second pair of buffers carries the number of edges jumped so far (terminals
+// add 0): integer sums are associative, so the depth below k is exact.
+// edge_valid may be null (every edge holds); edge_valid[k] is never read.
+__global__ __launch_bounds__(TB) void k_reroot_seed(const int32_t *__restrict__ parent,
+                                                    const uint8_t *__restrict__ edge_valid, int32_t n,
+                                                    int32_t k, uint32_t *__restrict__ w,
+                                                    uint32_t *__restrict__ d) {
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+    uint32_t x, e = 0;
+    if (i == k) {
+      x = (uint32_t)k << 1;
+    } else if (i == 0) {
+      x = 1u;
+    } else {
+      const int32_t p = parent[i];
+      const bool in = p >= 0 && p < n;
+      x = in ? ((uint32_t)p << 1) | ((edge_valid && !edge_valid[i]) ? 1u : 0u) : 1u;
+      e = in ? 1u : 0u;
+    }
+    w[i] = x;
+    d[i] = e;
+  }
+}
+
+__global__ __launch_bounds__(TB) void k_reroot_jump(const uint32_t *__restrict__ ws,
+                                                    const uint32_t *__restrict__ ds,
+                                                    uint32_t *__restrict__ wd,
+                                                    uint32_t *__restrict__ dd, int32_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+    const uint32_t x = ws[i], y = ws[x >> 1];
+    wd[i] = (y & ~1u) | ((x | y) & 1u);
+    dd[i] = ds[i] + ds[x >> 1];
+  }
+}
+
+// kept: below k with no failed edge in between (a vertex on a cycle of a
+// malformed parent array reaches neither terminal and is outside)
+__device__ __forceinline__ bool reroot_below(uint32_t w, int32_t k) { return (w >> 1) == (uint32_t)k; }
+__device__ __forceinline__ bool reroot_kept(uint32_t w, int32_t k) {
+  return reroot_below(w, k) && !(w & 1u);
+}
+
+// The prune's compaction with k taken out of the order: a tile counts its
+// kept vertices other than k, those below k whose own edge failed, those not
+// below k, and the largest depth of a kept vertex.
+__global__ __launch_bounds__(CB) void k_reroot_count(const uint32_t *__restrict__ w,
+                                                     const uint32_t *__restrict__ d,
+                                                     const uint8_t *__restrict__ edge_valid, int32_t n,
+                                                     int32_t k, uint4 *__restrict__ tile) {
+  __shared__ uint32_t sk[CB / WAVE], sb[CB / WAVE], so[CB / WAVE], sd[CB / WAVE];
+  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
+  const bool in = i < n;
+  const uint32_t x = in ? w[i] : 1u;
+  const bool below = in && reroot_below(x, k);
+  const bool keep = below && !(x & 1u);
+  const bool bad = below && i != k && edge_valid && !edge_valid[i];
+  const unsigned long long mk = __ballot(keep && i != k), mb = __ballot(bad), mo = __ballot(in && !below);
+  uint32_t dep = keep ? d[i] : 0u;
+#pragma unroll
+  for (int s = 1; s < WAVE; s <<= 1) dep = max(dep, (uint32_t)__shfl_xor(dep, s, WAVE));
+  if ((threadIdx.x & (WAVE - 1)) == 0) {
+    sk[threadIdx.x / WAVE] = (uint32_t)__popcll(mk);
+    sb[threadIdx.x / WAVE] = (uint32_t)__popcll(mb);
+    so[threadIdx.x / WAVE] = (uint32_t)__popcll(mo);
+    sd[threadIdx.x / WAVE] = dep;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint4 t = make_uint4(0u, 0u, 0u, 0u);
+    for (int q = 0; q < CB / WAVE; q++) {
+      t.x += sk[q];
+      t.y += sb[q];
+      t.z += so[q];
+      t.w = max(t.w, sd[q]);
+    }
+    tile[blockIdx.x] = t;
+  }
+}
+
+// one workgroup: toff[b] = 1 + the kept vertices other than k of the tiles
+// before b (k itself is vertex 0); the stats record and the tree's new count
+__global__ __launch_bounds__(CB) void k_reroot_scan(const uint4 *__restrict__ tile, int64_t ntile,
+                                                    uint32_t *__restrict__ toff, int32_t n,
+                                                    gbp_reroot_stats *__restrict__ stats,
+                                                    int32_t *__restrict__ count) {
+  __shared__ uint32_t ws[CB / WAVE], wb[CB / WAVE], wo[CB / WAVE], wd[CB / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  uint32_t run = 1, bad = 0, out = 0, deep = 0;  // the same in every thread
+  for (int64_t base = 0; base < ntile; base += CB) {
+    const int64_t b = base + threadIdx.x;
+    const uint4 c = b < ntile ? tile[b] : make_uint4(0u, 0u, 0u, 0u);
+    uint32_t incl = c.x, bsum = c.y, osum = c.z, dmax = c.w;
+#pragma unroll
+    for (int s = 1; s < WAVE; s <<= 1) {
+      const uint32_t up = __shfl_up(incl, s, WAVE);
+      if (lane >= s) incl += up;
+      bsum += __shfl_xor(bsum, s, WAVE);
+      osum += __shfl_xor(osum, s, WAVE);
+      dmax = max(dmax, (uint32_t)__shfl_xor(dmax, s, WAVE));
+    }
+    if (lane == WAVE - 1) ws[wv] = incl;
+    if (lane == 0) {
+      wb[wv] = bsum;
+      wo[wv] = osum;
+      wd[wv] = dmax;
+    }
+    __syncthreads();
+    uint32_t woff = 0, tot = 0;
+    for (int q = 0; q < CB / WAVE; q++) {
+      if (q < wv) woff += ws[q];
+      tot += ws[q];
+      bad += wb[q];
+      out += wo[q];
+      deep = max(deep, wd[q]);
+    }
+    if (b < ntile) toff[b] = run + woff + incl - c.x;
+    run += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    stats->n_before = n;
+    stats->n_kept = run;
+    stats->n_outside = out;
+    stats->n_edge_invalid = bad;
+    stats->n_inherited = (int64_t)n - run - bad - out;
+    stats->depth = deep;
+    *count = (int32_t)run;
+  }
+}
+
+// remap (k -> 0, the other kept vertices from 1 in their order), every kept
+// vertex's depth under its new index, and the levels' sizes (hist zeroed
+// before this launch; an integer count does not depend on the atomics' order)
+__global__ __launch_bounds__(CB) void k_reroot_rank(const uint32_t *__restrict__ w,
+                                                    const uint32_t *__restrict__ d, int32_t n, int32_t k,
+                                                    const uint32_t *__restrict__ toff,
+                                                    int32_t *__restrict__ remap,
+                                                    uint32_t *__restrict__ depth,
+                                                    uint32_t *__restrict__ hist) {
+  __shared__ uint32_t sk[CB / WAVE];
+  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const bool keep = i < n && reroot_kept(w[i], k);
+  const unsigned long long m = __ballot(keep && i != k);
+  if (lane == 0) sk[wv] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t off = toff[blockIdx.x];
+  for (int q = 0; q < wv; q++) off += sk[q];
+  if (i >= n) return;
+  const int32_t j = !keep ? -1 : i == k ? 0 : (int32_t)(off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)));
+  remap[i] = j;
+  if (j >= 0) {
+    depth[j] = d[i];
+    atomicAdd(&hist[d[i]], 1u);
+  }
+}
+
+// one workgroup, after the move: first[r] = the kept vertices of the levels
+// before r, r in [0, depth + 1] (hist keeps the sizes for k_reroot_order), and
+// the new root's action zeroed as k_tree_init writes it
+__global__ __launch_bounds__(CB) void k_reroot_levels(const uint32_t *__restrict__ hist,
+                                                      const gbp_reroot_stats *__restrict__ stats,
+                                                      uint32_t *__restrict__ first, double *__restrict__ a) {
+  __shared__ uint32_t ws[CB / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const int64_t nl = stats->depth + 1;
+  uint32_t run = 0;
+  for (int64_t base = 0; base < nl; base += CB) {
+    const int64_t r = base + threadIdx.x;
+    const uint32_t c = r < nl ? hist[r] : 0u;
+    uint32_t incl = c;
+#pragma unroll
+    for (int s = 1; s < WAVE; s <<= 1) {
+      const uint32_t up = __shfl_up(incl, s, WAVE);
+      if (lane >= s) incl += up;
+    }
+    if (lane == WAVE - 1) ws[wv] = incl;
+    __syncthreads();
+    uint32_t woff = 0, tot = 0;
+    for (int q = 0; q < CB / WAVE; q++) {
+      if (q < wv) woff += ws[q];
+      tot += ws[q];
+    }
+    if (r < nl) first[r] = run + woff + incl - c;
+    run += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) first[nl] = run;
+  if (threadIdx.x < 10) a[threadIdx.x] = 0.0;
+}
+
+// the counting sort's scatter: order[first[r] ..] = the vertices of level r.
+// Their order within a level depends on the atomics and is immaterial: a
+// vertex's g depends on its parent's alone.
+__global__ __launch_bounds__(TB) void k_reroot_order(const uint32_t *__restrict__ depth,
+                                                     const int32_t *__restrict__ count,
+                                                     const uint32_t *__restrict__ first,
+                                                     uint32_t *__restrict__ hist,
+                                                     int32_t *__restrict__ order) {
+  const int64_t m = *count;
+  for (int64_t j = (int64_t)blockIdx.x * TB + threadIdx.x; j < m; j += (int64_t)gridDim.x * TB) {
+    const uint32_t r = depth[j];
+    order[first[r] + atomicSub(&hist[r], 1u) - 1u] = (int32_t)j;
+  }
+}
+
+// g of one vertex from its parent's, as k_tree_load derives it
+__device__ __forceinline__ void reroot_g(const gbp_tree &t, int32_t c) {
+  const int32_t p = t.parent[c];
+  t.g[c] = p >= 0 ? t.g[p] + pose_distance(t.v + 8 * (int64_t)p, t.v + 8 * (int64_t)c) : 0.0;
+}
+
+// g by levels.  A level's vertices read the g their parents' level wrote: the
+// two are separated by a kernel boundary (a level wider than a workgroup is a
+// launch of its own over its slice of `order`) or by the barrier between the
+// steps of the one workgroup that walks a run of narrow levels.  No workgroup
+// waits for another.
+__global__ __launch_bounds__(TB) void k_reroot_g_wide(gbp_tree t, const int32_t *__restrict__ order,
+                                                      int64_t lo, int64_t hi) {
+  for (int64_t x = lo + (int64_t)blockIdx.x * TB + threadIdx.x; x < hi; x += (int64_t)gridDim.x * TB)
+    reroot_g(t, order[x]);
+}
+
+__global__ __launch_bounds__(TB) void k_reroot_g_narrow(gbp_tree t, const int32_t *__restrict__ order,
+                                                        const uint32_t *__restrict__ first, int64_t r0,
+                                                        int64_t r1) {
+  for (int64_t r = r0; r < r1; r++) {
+    const uint32_t x = first[r] + threadIdx.x;
+    if (x < first[r + 1]) reroot_g(t, order[x]);
+    __syncthreads();  // workgroup-scope release / acquire of the g just written
+  }
+}
+
 __global__ void k_plan_reset(gbp_plan_status *st, int64_t ext_counter, gbp_plan_la *la) {
   *la = gbp_plan_la{};  // no drawn-ahead targets, empty snapshots
   gbp_plan_status z;
@@ -3722,30 +3969,17 @@ int gbp_tree_prune_dev(gbp_tree *tree, int64_t n, const uint8_t *edge_valid, int
   return GBP_OK;
 }
 
-int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
-                             int32_t *remap, gbp_prune_stats *stats, int64_t *n_resolved) {
-  if (n_resolved) *n_resolved = 0;
-  if (!t || !tree_ok(tree)) return GBP_E_BAD_HANDLE;
-  if (!stats || (direction != GBP_FORWARD && direction != GBP_REVERSE)) return GBP_E_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
-  if (!t->d_z) return GBP_E_BAD_HANDLE;
-  DeviceGuard g(tree->device);
-  hipStream_t s = t->host_stream;
-  int64_t n = 0;
-  int rc = gbp_tree_size(tree, &n, s);
-  if (rc) return rc;
-  // edge_valid and flags back to back: one read-back
-  const size_t fl_at = ((size_t)n + 255) & ~(size_t)255;
+namespace {
+// The synchronous entries' edge decisions: stage A into dev (edge_valid[n],
+// then flags[n] at byte fl_at: one read-back), the FRAGILE edges re-decided
+// with glibc and edge_valid written back.  dev holds the final decisions and
+// nothing is in flight when this returns.
+int tree_edge_decisions(gbp_terrain *t, gbp_tree *tree, int64_t n, int direction, int adaptive,
+                        uint8_t *dev, size_t fl_at, int64_t *n_resolved, hipStream_t s) {
   const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
-  DevBuf buf;
-  uint8_t *dev;
-  int32_t *dmap;
-  gbp_prune_stats *dst;
-  rc = stage_buf(buf, [&](Stage &S) { S.take(dev, dec_bytes); S.take(dmap, n); S.take(dst, 1); });
-  if (rc) return rc;
   uint32_t *dfl = (uint32_t *)(dev + fl_at);
-  if ((rc = gbp_tree_revalidate_dev(t, tree, n, direction, adaptive, dev, dfl, s))) return rc;
+  int rc = gbp_tree_revalidate_dev(t, tree, n, direction, adaptive, dev, dfl, s);
+  if (rc) return rc;
   std::vector<uint8_t> dec(dec_bytes);
   if ((rc = d2h(dec.data(), dev, dec_bytes, s))) return rc;
   HIPCHK(hipStreamSynchronize(s));
@@ -3768,7 +4002,197 @@ int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int 
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(s));  // dec leaves scope only after the copy
   }
+  return GBP_OK;
+}
+}  // namespace
+
+int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
+                             int32_t *remap, gbp_prune_stats *stats, int64_t *n_resolved) {
+  if (n_resolved) *n_resolved = 0;
+  if (!t || !tree_ok(tree)) return GBP_E_BAD_HANDLE;
+  if (!stats || (direction != GBP_FORWARD && direction != GBP_REVERSE)) return GBP_E_INVALID_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
+  if (!t->d_z) return GBP_E_BAD_HANDLE;
+  DeviceGuard g(tree->device);
+  hipStream_t s = t->host_stream;
+  int64_t n = 0;
+  int rc = gbp_tree_size(tree, &n, s);
+  if (rc) return rc;
+  // edge_valid and flags back to back: one read-back
+  const size_t fl_at = ((size_t)n + 255) & ~(size_t)255;
+  const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
+  DevBuf buf;
+  uint8_t *dev;
+  int32_t *dmap;
+  gbp_prune_stats *dst;
+  rc = stage_buf(buf, [&](Stage &S) { S.take(dev, dec_bytes); S.take(dmap, n); S.take(dst, 1); });
+  if (rc) return rc;
+  if ((rc = tree_edge_decisions(t, tree, n, direction, adaptive, dev, fl_at, n_resolved, s))) return rc;
   if ((rc = gbp_tree_prune_dev(tree, n, dev, dmap, dst, s))) return rc;
+  if (remap && (rc = d2h(remap, dmap, n, s))) return rc;
+  if ((rc = d2h(stats, dst, 1, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  return GBP_OK;
+}
+
+// ---- re-rooting at a vertex ---------------------------------------
+namespace {
+// the last successful gbp_tree_reroot_dev of the process, for gbp_tree_reroot_last
+std::mutex reroot_last_mu;
+double reroot_last_ms[3] = {0, 0, 0};
+int64_t reroot_last_launches = 0;
+// the four marks between the call's three parts; a mark that could not be
+// created or recorded only leaves the times at zero
+struct RerootMarks {
+  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool ok = true;
+  RerootMarks() {
+    for (auto &x : e) ok = hipEventCreate(&x) == hipSuccess && ok;
+  }
+  ~RerootMarks() {
+    for (auto &x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  void mark(int k, hipStream_t s) { ok = ok && hipEventRecord(e[k], s) == hipSuccess; }
+};
+}  // namespace
+
+int gbp_tree_reroot_last(double ms[3], int64_t *launches) {
+  if (!ms || !launches) return GBP_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(reroot_last_mu);
+  for (int k = 0; k < 3; k++) ms[k] = reroot_last_ms[k];
+  *launches = reroot_last_launches;
+  return GBP_OK;
+}
+
+int gbp_tree_reroot_dev(gbp_tree *tree, int64_t n, int32_t new_root, const uint8_t *edge_valid,
+                        int32_t *remap, gbp_reroot_stats *stats, gbp_stream stream) {
+  int rc = prune_args(tree, n, remap && stats);
+  if (rc) return rc;
+  int64_t have = 0;
+  if ((rc = gbp_tree_size(tree, &have, stream))) return rc;  // synchronises
+  if (have != n) return GBP_E_SHAPE;
+  if (new_root < 0 || new_root >= n) return GBP_E_INVALID_ARG;
+  DeviceGuard g(tree->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t ntile = (n + CB - 1) / CB;
+  const int32_t k = new_root;
+  DevBuf buf;
+  uint32_t *w[2], *d[2], *toff, *depth, *hist, *first;
+  int32_t *order;
+  uint4 *tile;
+  rc = stage_buf(buf, [&](Stage &S) {
+    S.take(w[0], n); S.take(w[1], n); S.take(d[0], n); S.take(d[1], n); S.take(tile, ntile);
+    S.take(toff, ntile); S.take(depth, n); S.take(hist, n + 1); S.take(first, n + 2); S.take(order, n);
+  });
+  if (rc) return rc;
+  // as in the prune: fresh arrays, count and bounds, swapped in last
+  gbp_tree fresh = *tree;
+  if ((rc = tree_alloc(&fresh, tree->cap))) return rc;
+  fresh.count = nullptr;
+  fresh.hm = nullptr;
+  auto drop_fresh = [&](int code) {
+    (void)hipDeviceSynchronize();
+    tree_free_arrays(&fresh);
+    if (fresh.count) (void)hipFree(fresh.count);
+    if (fresh.hm) (void)hipFree(fresh.hm);
+    return code;
+  };
+  if (hipMalloc(&fresh.count, 4) != hipSuccess || hipMalloc(&fresh.hm, 64) != hipSuccess)
+    return drop_fresh(GBP_E_ALLOC);
+  const unsigned gv = grid_for(n, TB, 2048);
+  RerootMarks marks;
+  int64_t launches = 8;  // seed, count, scan, rank, two moves, levels, order
+  marks.mark(0, s);
+  hipLaunchKernelGGL(k_reroot_seed, dim3(gv), dim3(TB), 0, s, tree->parent, edge_valid, (int32_t)n, k, w[0],
+                     d[0]);
+  int cur = 0;  // ceil(log2 n) rounds, back to back
+  for (int64_t reach = 1; reach < n; reach <<= 1, cur ^= 1, launches++)
+    hipLaunchKernelGGL(k_reroot_jump, dim3(gv), dim3(TB), 0, s, w[cur], d[cur], w[cur ^ 1], d[cur ^ 1],
+                       (int32_t)n);
+  marks.mark(1, s);
+  hipLaunchKernelGGL(k_reroot_count, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], d[cur], edge_valid,
+                     (int32_t)n, k, tile);
+  hipLaunchKernelGGL(k_reroot_scan, dim3(1), dim3(CB), 0, s, tile, ntile, toff, (int32_t)n, stats,
+                     fresh.count);
+  bool ok = hipGetLastError() == hipSuccess && hipMemsetAsync(fresh.hm, 0, 64, s) == hipSuccess &&
+            hipMemsetAsync(hist, 0, (n + 1) * sizeof(uint32_t), s) == hipSuccess;
+  if (!ok) return drop_fresh(GBP_E_HIP);
+  hipLaunchKernelGGL(k_reroot_rank, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], d[cur], (int32_t)n, k,
+                     toff, remap, depth, hist);
+  // the prune's move: k's old parent is not kept, so parent[0] = -1 and the
+  // new root is in no list; the g copied here is written again below
+  hipLaunchKernelGGL(k_prune_move_rows, dim3(grid_for(n * PRUNE_PIECES, TB, 2048)), dim3(TB), 0, s, *tree,
+                     fresh, (int32_t)n, remap);
+  hipLaunchKernelGGL(k_prune_move_links, dim3(gv), dim3(TB), 0, s, *tree, fresh, (int32_t)n, remap);
+  hipLaunchKernelGGL(k_reroot_levels, dim3(1), dim3(CB), 0, s, hist, stats, first, fresh.a);
+  hipLaunchKernelGGL(k_reroot_order, dim3(gv), dim3(TB), 0, s, depth, fresh.count, first, hist, order);
+  marks.mark(2, s);
+  if (hipGetLastError() != hipSuccess) return drop_fresh(GBP_E_HIP);
+  // the levels' sizes decide the launches of g
+  gbp_reroot_stats hs;
+  if (d2h(&hs, stats, 1, s) || hipStreamSynchronize(s) != hipSuccess) return drop_fresh(GBP_E_HIP);
+  const int64_t nl = hs.depth + 1;
+  if (hs.n_kept < 1 || hs.n_kept > n || nl < 1 || nl > hs.n_kept) return drop_fresh(GBP_E_HIP);
+  std::vector<uint32_t> lv(nl + 1);
+  if (d2h(lv.data(), first, nl + 1, s) || hipStreamSynchronize(s) != hipSuccess)
+    return drop_fresh(GBP_E_HIP);
+  for (int64_t r = 0; r < nl; launches++) {
+    if (lv[r + 1] - lv[r] > (uint32_t)TB) {
+      hipLaunchKernelGGL(k_reroot_g_wide, dim3(grid_for(lv[r + 1] - lv[r], TB, 2048)), dim3(TB), 0, s, fresh,
+                         order, (int64_t)lv[r], (int64_t)lv[r + 1]);
+      r++;
+      continue;
+    }
+    int64_t e = r + 1;  // a run of levels no wider than a workgroup
+    while (e < nl && lv[e + 1] - lv[e] <= (uint32_t)TB) e++;
+    hipLaunchKernelGGL(k_reroot_g_narrow, dim3(1), dim3(TB), 0, s, fresh, order, first, r, e);
+    r = e;
+  }
+  marks.mark(3, s);
+  ok = hipGetLastError() == hipSuccess;
+  if (hipStreamSynchronize(s) != hipSuccess || !ok) return drop_fresh(GBP_E_HIP);
+  {
+    std::lock_guard<std::mutex> lk(reroot_last_mu);
+    for (int q = 0; q < 3; q++) {
+      float t = 0.f;
+      reroot_last_ms[q] = marks.ok && hipEventElapsedTime(&t, marks.e[q], marks.e[q + 1]) == hipSuccess ? t : 0.0;
+    }
+    reroot_last_launches = launches;
+  }
+  tree_free_arrays(tree);
+  (void)hipFree(tree->count);
+  (void)hipFree(tree->hm);
+  *tree = fresh;
+  return GBP_OK;
+}
+
+int gbp_tree_reroot_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, int direction,
+                         int adaptive, int32_t *remap, gbp_reroot_stats *stats, int64_t *n_resolved) {
+  if (n_resolved) *n_resolved = 0;
+  if (!tree_ok(tree)) return GBP_E_BAD_HANDLE;
+  if (!stats || (t && direction != GBP_FORWARD && direction != GBP_REVERSE)) return GBP_E_INVALID_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
+  if (t && !t->d_z) return GBP_E_BAD_HANDLE;
+  DeviceGuard g(tree->device);
+  hipStream_t s = t ? t->host_stream : nullptr;
+  int64_t n = 0;
+  int rc = gbp_tree_size(tree, &n, s);
+  if (rc) return rc;
+  if (new_root < 0 || new_root >= n) return GBP_E_INVALID_ARG;
+  const size_t fl_at = ((size_t)n + 255) & ~(size_t)255;
+  const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
+  DevBuf buf;
+  uint8_t *dev;
+  int32_t *dmap;
+  gbp_reroot_stats *dst;
+  rc = stage_buf(buf, [&](Stage &S) { S.take(dev, dec_bytes); S.take(dmap, n); S.take(dst, 1); });
+  if (rc) return rc;
+  if (t && (rc = tree_edge_decisions(t, tree, n, direction, adaptive, dev, fl_at, n_resolved, s)))
+    return rc;
+  if ((rc = gbp_tree_reroot_dev(tree, n, new_root, t ? dev : nullptr, dmap, dst, s))) return rc;
   if (remap && (rc = d2h(remap, dmap, n, s))) return rc;
   if ((rc = d2h(stats, dst, 1, s))) return rc;
   HIPCHK(hipStreamSynchronize(s));

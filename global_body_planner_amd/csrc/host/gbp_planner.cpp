@@ -1396,6 +1396,49 @@ void RRTConnectClass::revalidateTrees(FastTerrainMap &terrain, TreeDump &trees, 
   }
 }
 
+void RRTConnectClass::rerootStartTree(FastTerrainMap &terrain, TreeDump &trees, int32_t vertex,
+                                      RerootStats &stats, std::vector<int32_t> *remap,
+                                      bool test_edges) {
+  struct Tree {  // the device tree of this call
+    gbp_tree *t = nullptr;
+    ~Tree() {
+      if (t) gbp_tree_destroy(t);
+    }
+  };
+  const int64_t n = (int64_t)trees.v[0].size();
+  if (n < 1 || (int64_t)trees.a[0].size() != n || (int64_t)trees.parent[0].size() != n ||
+      (int64_t)trees.g[0].size() != n)
+    throw EngineError(GBP_E_INVALID_ARG, "rerootStartTree: tree arrays");
+  Tree T;
+  chk(gbp_tree_create(terrain.device(), n, &T.t), "rerootStartTree: tree");
+  chk(gbp_tree_load_host(T.t, n, trees.v[0][0].data(), trees.a[0][0].data(), trees.parent[0].data(),
+                         nullptr),
+      "rerootStartTree: tree load");
+  std::vector<int32_t> map(n);
+  gbp_reroot_stats rs{};
+  RerootStats done;
+  chk(gbp_tree_reroot_host(test_edges ? terrain.handle() : nullptr, T.t, vertex, FORWARD,
+                           state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0, map.data(), &rs,
+                           &done.fragile_resolved),
+      "rerootStartTree");
+  done.n_before = rs.n_before;
+  done.n_kept = rs.n_kept;
+  done.n_outside = rs.n_outside;
+  done.n_edge_invalid = rs.n_edge_invalid;
+  done.n_inherited = rs.n_inherited;
+  done.depth = rs.depth;
+  // the survivors from the host copy (the device moved the same rows), g from
+  // the device: it is derived again there
+  TreeDump kept = trees;
+  if (!applyRerootRemap(map, vertex, kept, 0) || (int64_t)kept.v[0].size() != done.n_kept)
+    throw EngineError(GBP_E_INVALID_ARG, "rerootStartTree: remap");
+  chk(gbp_tree_read(T.t, 0, done.n_kept, nullptr, nullptr, nullptr, kept.g[0].data(), nullptr),
+      "rerootStartTree: g");
+  trees = std::move(kept);
+  stats = done;
+  if (remap) *remap = std::move(map);
+}
+
 bool RRTConnectClass::buildRRTConnectBatched(FastTerrainMap &terrain, State s_start, State s_goal,
                                              int batch, double max_time,
                                              std::vector<State> &state_sequence,

@@ -3,6 +3,7 @@
 #include "gbp_tree_path.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace gbp_amd {
 
@@ -16,6 +17,30 @@ std::vector<int> pathFromRoot(const int *parent, int idx) {
   }
   std::reverse(path.begin(), path.end());
   return path;
+}
+
+std::vector<int> startTreePath(const std::vector<int32_t> &parent, int32_t meet_a) {
+  const int64_t n = (int64_t)parent.size();
+  std::vector<int> path;
+  if (meet_a < 0 || meet_a >= n) return path;
+  int32_t idx = meet_a;
+  for (int64_t steps = 0; steps < n; steps++) {
+    path.push_back(idx);
+    if (idx == 0) {
+      std::reverse(path.begin(), path.end());
+      return path;
+    }
+    idx = parent[idx];
+    if (idx < 0 || idx >= n) break;
+  }
+  return {};
+}
+
+int findStateAmong(const std::vector<State> &v, const std::vector<int> &vertices, const State &s) {
+  for (int i : vertices)
+    if (i >= 0 && (size_t)i < v.size() && std::memcmp(v[i].data(), s.data(), sizeof(State)) == 0)
+      return i;
+  return -1;
 }
 
 double pathDuration(const std::vector<Action> &actions) {

@@ -30,6 +30,17 @@ struct JoinedPath {
 // rrt.cpp:107-118: the vertices root -> idx
 std::vector<int> pathFromRoot(const int *parent, int idx);
 
+// The robot has moved along a found path: the start tree's vertices the path
+// runs over, root -> meet_a (BatchStats::meet_a), from a dumped tree's
+// parents; empty when meet_a is no vertex of the tree or the chain does not
+// end at the root within the tree's size.
+std::vector<int> startTreePath(const std::vector<int32_t> &parent, int32_t meet_a);
+
+// Which of `vertices` (indices into v) holds exactly state s, all eight
+// values bit for bit: a post-processed path keeps tree states but not tree
+// indices.  The first match, or -1.
+int findStateAmong(const std::vector<State> &v, const std::vector<int> &vertices, const State &s);
+
 // sum of stance + flight time over the actions
 double pathDuration(const std::vector<Action> &actions);
 

@@ -43,4 +43,52 @@ bool applyPruneRemap(const std::vector<int32_t> &remap, TreeDump &trees, int k) 
   return true;
 }
 
+int64_t applyRerootRemap(const int32_t *remap, int64_t n, int32_t new_root, State *v, Action *a,
+                         int32_t *parent, double *g) {
+  if (n < 1 || !remap || !v || !a || !parent || new_root < 0 || new_root >= n || remap[new_root] != 0)
+    return -1;
+  // the whole map is checked before the first row moves
+  int64_t kept = 1;
+  for (int64_t i = 0; i < n; i++) {
+    if (i == new_root || remap[i] < 0) continue;
+    if (remap[i] != kept) return -1;
+    if (parent[i] < 0 || parent[i] >= n || remap[parent[i]] < 0) return -1;
+    kept++;
+  }
+  // the new root's row is set aside: a later row may land on its place.  Every
+  // other kept row moves down or stays (vertex 0 is not kept unless it is the
+  // new root, so at most i - 1 kept rows precede row i), and never onto row 0.
+  const State root_v = v[new_root];
+  const double root_g = g ? g[new_root] : 0.0;
+  for (int64_t i = 0; i < n; i++) {
+    const int64_t j = remap[i];
+    if (i == new_root || j < 0) continue;
+    const int32_t p = parent[i];
+    v[j] = v[i];
+    a[j] = a[i];
+    if (g) g[j] = g[i];
+    parent[j] = remap[p];
+  }
+  v[0] = root_v;
+  a[0].fill(0.0);
+  if (g) g[0] = root_g;
+  parent[0] = -1;
+  return kept;
+}
+
+bool applyRerootRemap(const std::vector<int32_t> &remap, int32_t new_root, TreeDump &trees, int k) {
+  const size_t n = remap.size();
+  if (k < 0 || k > 1 || trees.v[k].size() != n || trees.a[k].size() != n ||
+      trees.parent[k].size() != n || trees.g[k].size() != n)
+    return false;
+  const int64_t kept = applyRerootRemap(remap.data(), (int64_t)n, new_root, trees.v[k].data(),
+                                        trees.a[k].data(), trees.parent[k].data(), trees.g[k].data());
+  if (kept < 0) return false;
+  trees.v[k].resize(kept);
+  trees.a[k].resize(kept);
+  trees.parent[k].resize(kept);
+  trees.g[k].resize(kept);
+  return true;
+}
+
 }  // namespace gbp_amd

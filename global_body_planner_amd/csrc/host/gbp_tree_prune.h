@@ -1,5 +1,6 @@
-// gbp_tree_prune.h — a prune's remap (gbp_tree_prune_dev, include/gbp.h)
-// applied to the host copy of a tree.  Pure host code with no engine call.
+// gbp_tree_prune.h — a prune's remap (gbp_tree_prune_dev, include/gbp.h) or a
+// re-root's (gbp_tree_reroot_dev) applied to the host copy of a tree.  Pure
+// host code with no engine call.
 #pragma once
 
 #include <cstdint>
@@ -20,5 +21,19 @@ int64_t applyPruneRemap(const int32_t *remap, int64_t n, State *v, Action *a, in
 
 // tree k of a TreeDump (its four vectors shortened to the survivors)
 bool applyPruneRemap(const std::vector<int32_t> &remap, TreeDump &trees, int k);
+
+// remap[n] as the device re-root returns it: new_root numbered 0, the other
+// kept vertices 1, 2, ... in ascending old index, a kept vertex other than
+// new_root under a kept parent.  Moves the kept rows to the front in place:
+// the new root first, its action zeroed and its parent -1, parent elsewhere as
+// remap[parent].  g's rows (g may be null) are moved as they are: a re-root
+// derives g again from the new root, and the caller takes it from the device
+// tree.  Returns how many rows are kept; -1, with nothing changed, when remap
+// is no such map for these parents.
+int64_t applyRerootRemap(const int32_t *remap, int64_t n, int32_t new_root, State *v, Action *a,
+                         int32_t *parent, double *g);
+
+// tree k of a TreeDump (its four vectors shortened to the survivors)
+bool applyRerootRemap(const std::vector<int32_t> &remap, int32_t new_root, TreeDump &trees, int k);
 
 }  // namespace gbp_amd

@@ -506,6 +506,29 @@ class DeviceTree:
         stats["n_resolved"] = k.value
         return remap, stats
 
+    def reroot(self, vertex, terrain=None, direction=L.FORWARD, adaptive=False):
+        """gbp_tree_reroot_host: makes `vertex` the root and keeps the subtree
+        below it, in HBM.  The new root becomes vertex 0 (action zeroed, parent
+        -1), the other kept vertices follow in ascending old index, and g is
+        derived again from the new root down.  With `terrain` (an
+        engine.Terrain holding a changed map) the edges are tested on it as
+        revalidate does, and a vertex below the new root stays only when every
+        edge between the two holds.  Returns (remap, stats): remap [n before]
+        int32, a vertex's new index or -1; stats a dict of n_before, n_kept,
+        n_outside (not below the new root), n_edge_invalid, n_inherited (below
+        it: own edge failed / an ancestor's did), depth (most edges between
+        the new root and a kept vertex) and n_resolved."""
+        remap = np.empty(len(self), np.int32)
+        st = L.RerootStats()
+        k = ctypes.c_int64(0)
+        check(self._lib.gbp_tree_reroot_host(terrain._h if terrain is not None else None, self._h,
+                                             int(vertex), int(direction), int(bool(adaptive)),
+                                             _np_ptr(remap), ctypes.byref(st), ctypes.byref(k)),
+              "tree_reroot")
+        stats = {name: getattr(st, name) for name, _ in L.RerootStats._fields_}
+        stats["n_resolved"] = k.value
+        return remap, stats
+
     def read(self):
         """(states [n][8], actions [n][10], parents [n], g [n]) numpy."""
         n = len(self)

@@ -332,6 +332,39 @@ def revalidate_trees(data, trees, adaptive=False, device=0):
     return tuple(pruned), tuple(remaps), tuple(stats)
 
 
+def reroot_tree(tree, vertex, data=None, adaptive=False, device=0):
+    """The start tree of an earlier search once the robot stands on one of its
+    vertices: what of it the next search, from that state, may start from.
+
+    tree: a dict of v [n][8], act [n][10], parent [n] (tree a of
+    plan_rrt_connect(..., trees=True): grown FORWARD).  It is loaded into HBM
+    and re-rooted there (engine.DeviceTree.reroot): `vertex` becomes vertex 0
+    and the subtree below it follows in ascending old index; everything else
+    is unreachable, because the dynamics are not reversible.  With `data`
+    (terrain_data.TerrainData, or an engine.Terrain) the map has changed too:
+    the edges are tested FORWARD on it and a vertex stays only when every edge
+    between it and the new root holds.  Returns (tree, remap, stats): the
+    survivors as a dict of v, act, parent and g (derived again from the new
+    root), the int32 map from an old index to the new one (-1: dropped), the
+    stats dict.  The next search is plan_rrt_connect(data, tree["v"][0], goal,
+    init_trees=(tree, b))."""
+    from . import engine
+    own = data is not None and not isinstance(data, engine.Terrain)
+    T = engine.Terrain.from_data(data, device=device) if own else data
+    try:
+        v = np.ascontiguousarray(tree["v"], np.float64).reshape(-1, 8)
+        dt = engine.DeviceTree(v[0], device=device if T is None else T.device,
+                               capacity=max(v.shape[0], 1))
+        dt.load(v, tree["act"], tree["parent"])
+        remap, stats = dt.reroot(vertex, T, _lib.FORWARD, adaptive=adaptive)
+        s, a, p, g = dt.read()
+        del dt
+    finally:
+        if own:
+            T.close()
+    return dict(v=s, act=a, parent=p, g=g), remap, stats
+
+
 def attempt_connect(terrain, s_existing, s, direction, t_s=None, adaptive=False, s_new=None,
                     a_new=None):
     """RRTConnectClass::attemptConnect (rrt_connect.cpp:20-91) for n pairs on an

@@ -571,6 +571,57 @@ int gbp_tree_prune_dev(gbp_tree *tree, int64_t n, const uint8_t *edge_valid, int
 int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
                              int32_t *remap, gbp_prune_stats *stats, int64_t *n_resolved);
 
+/* ---- a tree re-rooted at one of its vertices ----------------------------------
+ * The robot executes its plan: at the next call it stands on a later state of
+ * the path, a vertex k of the forward-grown start tree.  The dynamics are not
+ * reversible, so what the next search may reuse of that tree is the subtree
+ * below k.  Vertex i is kept when k lies on i's parent chain (i = k included)
+ * and every edge (parent[j] -> j), j on the chain from i up to but excluding
+ * k, has edge_valid[j] = 1; edge_valid[k] and everything above k are ignored.
+ * k becomes vertex 0 (its action ten zeros, its parent -1, as gbp_tree_init
+ * writes them) and the other kept vertices follow in ascending old index; in
+ * a tree whose parents precede their children the result has them so again.
+ * g is derived again from the new root down, g[c] = g[parent[c]] +
+ * poseDistance(v[parent[c]], v[c]) with g[0] = 0, as gbp_tree_load_host
+ * derives it (not g - g[k], which differs in the last bits). */
+typedef struct {
+  int64_t n_before;        /* vertices of the tree before the call                 */
+  int64_t n_kept;          /* ... and after it                                     */
+  int64_t n_outside;       /* dropped: not below new_root                          */
+  int64_t n_edge_invalid;  /* dropped: below it, own edge failed                   */
+  int64_t n_inherited;     /* dropped: below it, only because an ancestor was      */
+  int64_t depth;           /* most edges between the new root and a kept vertex    */
+} gbp_reroot_stats;
+/* Device edge_valid[n] (NULL: every edge holds), remap[n] = a vertex's new
+ * index or -1, stats[1].  The kept rows of v / a are moved, parent =
+ * remap[parent], g derived, the fp16 search rows, the search bounds and the
+ * successor lists rebuilt from the kept rows, the count set; the capacity
+ * stays.  As in gbp_tree_prune_dev the rows go into fresh arrays that replace
+ * the tree's (pointers from gbp_tree_device_ptrs are stale afterwards) and the
+ * swap is the last step: a call that returns an error leaves the tree as it
+ * was (remap and stats may have been written).  Synchronises the stream:
+ * before, to compare n with the device's count (GBP_E_SHAPE when they differ);
+ * in between, to read the levels' sizes that decide the launches of g; and
+ * after.  GBP_E_INVALID_ARG when new_root is outside [0, n).  new_root = 0
+ * with edge_valid = NULL is the identity. */
+int gbp_tree_reroot_dev(gbp_tree *tree, int64_t n, int32_t new_root, const uint8_t *edge_valid,
+                        int32_t *remap, gbp_reroot_stats *stats, gbp_stream stream);
+/* Diagnostics (tools/tree_reroot_ab.py): of the process's last successful
+ * gbp_tree_reroot_dev, the device time in milliseconds between stream events
+ * of its three parts (the keep rule and depth; the compaction, the move and
+ * the sort by depth; g by levels, the wait for the levels' sizes included) and
+ * the kernels it launched. */
+int gbp_tree_reroot_last(double ms[3], int64_t *launches);
+/* Synchronous.  t == NULL: no edge is tested (direction and adaptive are
+ * ignored).  Otherwise stage A of the prune (gbp_tree_revalidate_dev) on t, on
+ * the terrain's own stream, the FRAGILE edges re-decided with glibc
+ * (*n_resolved, may be NULL), then the re-root under those decisions: the
+ * robot has moved and the map has changed, in one pass.  Host remap[size of
+ * the tree before] (may be NULL) and stats[1].  GBP_E_INVALID_ARG when
+ * new_root is outside the tree or the direction is bad; the tree is unchanged. */
+int gbp_tree_reroot_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, int direction,
+                         int adaptive, int32_t *remap, gbp_reroot_stats *stats, int64_t *n_resolved);
+
 /* ---- the device planner loop (RRTConnectClass::runRRTConnect,
  *      rrt_connect.cpp:230-314, batch-synchronous) ---------------------------
  * One half-iteration, enqueued on `stream` without any host synchronisation:

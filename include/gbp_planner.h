@@ -507,6 +507,18 @@ struct PruneStats {
   int64_t fragile_resolved = 0;
 };
 
+// What RRTConnectClass::rerootStartTree did (gbp_reroot_stats, include/gbp.h,
+// and the FRAGILE edges re-decided on the host with glibc).
+struct RerootStats {
+  int64_t n_before = 0;        // vertices of the start tree before
+  int64_t n_kept = 0;          // ... and after: the new root and what stays below it
+  int64_t n_outside = 0;       // dropped: not below the new root
+  int64_t n_edge_invalid = 0;  // dropped: below it, own edge failed on the map
+  int64_t n_inherited = 0;     // dropped: below it, only because an ancestor was
+  int64_t depth = 0;           // most edges between the new root and a kept vertex
+  int64_t fragile_resolved = 0;
+};
+
 class RRTConnectClass : public RRTClass {
  public:
   // rrt_connect.cpp:20-84 (recursive; the pair checks run on the engine)
@@ -589,6 +601,23 @@ class RRTConnectClass : public RRTClass {
   // stats and remap as they were.
   void revalidateTrees(FastTerrainMap &terrain, TreeDump &trees, PruneStats stats[2],
                        std::vector<int32_t> remap[2] = nullptr);
+
+  // The robot moved: at the next call it stands on `vertex` of the start tree
+  // (tree 0 of an earlier search's dump, grown FORWARD; gbp_tree_path.h finds
+  // the vertex of a path state).  The tree is loaded into HBM and re-rooted
+  // there (gbp_tree_reroot_host): `vertex` becomes vertex 0, the subtree below
+  // it follows in ascending old index, and the rest goes, because the dynamics
+  // are not reversible.  With test_edges the map changed as well: the edges
+  // are tested FORWARD on `terrain` (this object's adaptive-step flag, FRAGILE
+  // ones re-decided with glibc) and a vertex stays only when every edge
+  // between it and the new root holds.  Tree 0 of `trees` is left holding the
+  // survivors with g derived again from the new root, ready for
+  // BatchStats::warm_* of a search from trees.v[0][0]; tree 1 is not touched
+  // (revalidateTrees prunes it when the map changed).  remap (optional)
+  // receives each old vertex's new index or -1.  A call that throws
+  // (EngineError) leaves trees, stats and remap as they were.
+  void rerootStartTree(FastTerrainMap &terrain, TreeDump &trees, int32_t vertex, RerootStats &stats,
+                       std::vector<int32_t> *remap = nullptr, bool test_edges = false);
 
   // attemptConnect for many independent pairs (lock-step rounds, one engine
   // launch per recursion depth); s_new / a_new are in/out per pair
