@@ -27,6 +27,7 @@ OPT_AFFINE_COORDS, OPT_COORD_MODE, OPT_XCD_MAP, OPT_FAST_RCP, OPT_FRAGILE_EPS = 
 OPT_NN_STATS = 18
 OPT_REFILL_WINDOW = 19
 OPT_LAUNCH_BLOCK = 20
+OPT_NAN_FREE, OPT_NAN_TESTS = 21, 22
 PLAN_HALT_TARGETS, PLAN_HALT_EXTEND, PLAN_HALT_CONNECT = 1, 2, 4
 PLAN_HALT_STAR, PLAN_HALT_STAR_PAIRS = 8, 16
 KERNEL_DIRECT, KERNEL_PERSISTENT = 0, 1

@@ -517,7 +517,13 @@ __device__ __forceinline__ double probe_height_bf(const TerrainView<ZT> &T, cons
 // anyway and pays the exec-mask bookkeeping on top; here the wave issues one
 // path.  Same values, same decisions, same G/V and flags as the reference's
 // executed calls.
-template <class ZT, int CM = 0, bool ONE = false>
+// NF: the host has verified that no height of the map is NaN (the handle's
+// nan_free, gbp_internal.h).  heightIsNan is then its UB test alone — -1 where
+// a coordinate is at or beyond the last grid line (BR_HIGH is exactly v >= d[n-1]
+// in both bracket forms; a NaN coordinate is BR_LOW), else 0 — so the centre
+// needs no bracket, no cell and no gather, the legs no isnan, and GBP_F_NAN
+// cannot be set.  Everything else is the same code.
+template <class ZT, int CM = 0, bool ONE = false, bool NF = false>
 __device__ bool is_valid_state(const TerrainView<ZT> &T, const double *s, int phase, Acc &acc) {
   if (acc.V >= GBP_MAX_SAMPLES) {  // engine guard: the reference loop would not terminate
     acc.flags |= GBP_F_LIMIT;
@@ -531,8 +537,8 @@ __device__ bool is_valid_state(const TerrainView<ZT> &T, const double *s, int ph
   // with the nine others (one round trip per state check, not two)
   double cy, sy, cp, sp;
   rotation_trig_nolibm(s[3], s[4], speed, s[6], cy, sy, cp, sp);
-  Probe<ZT> pc;
-  probe<ZT, CM, ONE>(T, s[0], s[1], pc);
+  [[maybe_unused]] Probe<ZT> pc;
+  if constexpr (!NF) probe<ZT, CM, ONE>(T, s[0], s[1], pc);
   // A state heading along +x with zero pitch (dy = +-0, dx > 0, p = +-0: every
   // start / goal state of the reference node, global_body_planner.cpp:219-264)
   // has exactly glibc's trig values: atan2(+-0, dx) = +-0 -> (1, +-0), and
@@ -559,9 +565,11 @@ __device__ bool is_valid_state(const TerrainView<ZT> &T, const double *s, int ph
   uint32_t fl = 0;
   // (1) heightIsNan(centre) :564 (x or y >= the last coordinate: UB, rejected
   //     by (2) unless exactly equal)
-  const int r = probe_nan(pc);
+  int r;
+  if constexpr (NF) r = ((s[0] >= T.xN) | (s[1] >= T.yN)) ? -1 : 0;
+  else r = probe_nan(pc);
   if (r < 0 && !outside) fl |= GBP_F_OOD;
-  if (r > 0) fl |= GBP_F_NAN;
+  if (!NF && r > 0) fl |= GBP_F_NAN;
   // (2) bounds + |pitch| :568-571, (3) horizontal speed :574
   bool alive = r == 0 && !(outside || (fabs(s[6]) >= P_MAX)) && !(speed > V_MAX);
   uint32_t G = 0;
@@ -576,7 +584,9 @@ __device__ bool is_valid_state(const TerrainView<ZT> &T, const double *s, int ph
     const double x_corner = x_leg + R_13 * z_body;
     const double y_corner = y_leg + R_23 * z_body;
     const double z_corner = z_leg + R_33 * z_body;
-    const int rl = probe_nan(pl[k]);  // heightIsNan(leg) :614
+    int rl;  // heightIsNan(leg) :614
+    if constexpr (NF) rl = ((pl[k].ix == BR_HIGH) | (pl[k].iy == BR_HIGH)) ? -1 : 0;
+    else rl = probe_nan(pl[k]);
     bool okl, okc, nl, nc;
     const double gl = probe_height_bf<ZT, CM>(T, pl[k], x_leg, y_leg, feps, okl, nl);
     const double gc = probe_height_bf<ZT, CM>(T, pk[k], x_corner, y_corner, feps, okc, nc);
@@ -585,7 +595,7 @@ __device__ bool is_valid_state(const TerrainView<ZT> &T, const double *s, int ph
     // the map edge (OOD <-> in domain) as well as give another height
     if (alive && nl) fl |= GBP_F_FRAGILE;
     if (alive && rl < 0) fl |= GBP_F_OOD;
-    if (alive && rl > 0) fl |= GBP_F_NAN;
+    if (!NF && alive && rl > 0) fl |= GBP_F_NAN;
     alive = alive && rl == 0;
     G += alive ? 2u : 0u;  // both heights computed before the test :618-619
     if (alive && !okl) fl |= GBP_F_OOD;

@@ -236,7 +236,15 @@ inline size_t rows_bytes(int block) {
 template <class ZT, int W, int CM, bool ONE>
 constexpr bool refill_ring = W <= 2 && sizeof(ZT) == 4 && !(CM == 0 && ONE);
 
-template <class ZT, bool ADAPTIVE, int W, int CM, bool ONE, bool RING>
+// The state check without its NaN tests and centre probe (is_valid_state's NF,
+// DESIGN section 5.1), for handles whose map holds no NaN height: compiled for
+// the forms that carry the headline and the planner loop only (fp32 heights,
+// not adaptive, W = 2, coordinates in LDS or computed), with and without the
+// ring; every other form keeps the general check whatever the map holds.
+template <class ZT, bool AD, int W, int CM, bool ONE>
+constexpr bool nan_free_form = sizeof(ZT) == 4 && !AD && W == 2 && CM != 0 && ONE;
+
+template <class ZT, bool ADAPTIVE, int W, int CM, bool ONE, bool RING, bool NF = false>
 __global__ __launch_bounds__(512, W) void k_validate_persistent(
     TerrainView<ZT> T0, int n, const double *__restrict__ S, const double *__restrict__ A,
     const uint8_t *__restrict__ dir, int dir_all, uint8_t *__restrict__ valid,
@@ -461,7 +469,7 @@ __global__ __launch_bounds__(512, W) void k_validate_persistent(
       sample_state(ps, ps + 8, st, t_eval, sc);
       // ONE (a template parameter, so the kernel holds one bracket form and
       // its registers): the terrain's one-step guess is exact on both axes
-      ok = is_valid_state<ZT, CM, ONE>(T, sc, stage_phase(st), acc_s);
+      ok = is_valid_state<ZT, CM, ONE, NF>(T, sc, stage_phase(st), acc_s);
     }
     LP_T(t3);
     LP_ADD(2, t2, t3);
@@ -1022,8 +1030,17 @@ int launch_validate_w(gbp_terrain *t, int64_t n, const double *s, const double *
                            s + 8 * off, a + 10 * off, d, dir_all, v, sn, tn, flags + off, c, n_dev,
                            (int)t->opt_helpers, (int)t->opt_xcd_map);
       };
-      if (ring) go(k_validate_persistent<ZT, AD, W, CM, ONE, CAN>);
-      else go(k_validate_persistent<ZT, AD, W, CM, ONE, false>);
+      // no NaN height in the map (host-verified, no device update pending) and
+      // the general check not forced: the form without the NaN tests
+      constexpr bool NFF = nan_free_form<ZT, AD, W, CM, ONE>;
+      const bool nf = NFF && nan_free_now(t) && !t->opt_nan_tests;
+      if (ring) {
+        if (nf) go(k_validate_persistent<ZT, AD, W, CM, ONE, CAN, NFF>);
+        else go(k_validate_persistent<ZT, AD, W, CM, ONE, CAN>);
+      } else {
+        if (nf) go(k_validate_persistent<ZT, AD, W, CM, ONE, false, NFF>);
+        else go(k_validate_persistent<ZT, AD, W, CM, ONE, false>);
+      }
     }
     HIPCHK(hipGetLastError());
   }
@@ -1311,6 +1328,7 @@ int gbp_terrain_create(int device, int nx, int ny, const double *x, const double
   t->host.z.resize(cells);
   for (size_t i = 0; i < cells; i++)  // exactly what the device holds
     t->host.z[i] = storage == GBP_STORAGE_F32 ? (double)(float)z[i] : z[i];
+  t->nan_free = gbp_patch::nan_free(t->host.z.data(), cells) ? 1 : 0;
   (void)hipDeviceGetAttribute(&t->num_cus, hipDeviceAttributeMultiprocessorCount, device);
   if (t->num_cus <= 0) t->num_cus = 256;
   int rc = GBP_OK;
@@ -1428,6 +1446,9 @@ int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value) {
     case GBP_OPT_NN_STATS:
       t->opt_nn_stats = value ? 1 : 0;
       return GBP_OK;
+    case GBP_OPT_NAN_TESTS:
+      t->opt_nan_tests = value ? 1 : 0;
+      return GBP_OK;
     case GBP_OPT_FRAGILE_EPS:  // in 1e-15 units; never below the default margin
       if (value < 1000 || value > 1000000000000000LL) return GBP_E_INVALID_ARG;
       t->fragile_eps = (double)value * 1e-15;
@@ -1451,6 +1472,8 @@ int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value) {
     case GBP_OPT_XCD_MAP: *value = t->opt_xcd_map; return GBP_OK;
     case GBP_OPT_FAST_RCP: *value = t->opt_fast_rcp ? (t->rcp_seed != 0.0 ? 1 : 0) : 0; return GBP_OK;
     case GBP_OPT_NN_STATS: *value = t->opt_nn_stats; return GBP_OK;
+    case GBP_OPT_NAN_FREE: *value = nan_free_now(t) ? 1 : 0; return GBP_OK;
+    case GBP_OPT_NAN_TESTS: *value = t->opt_nan_tests; return GBP_OK;
     case GBP_OPT_FRAGILE_EPS: *value = (int64_t)std::llround(t->fragile_eps * 1e15); return GBP_OK;
     case GBP_OPT_COORD_MODE:  // what the validate kernel of the current options uses
       *value = validate_coord_mode(t, t->opt_kernel == GBP_KERNEL_DIRECT);

@@ -40,6 +40,10 @@ struct gbp_terrain {
   int64_t opt_affine = 1;           // compute coordinates when the affine form is exact
   int64_t opt_fast_rcp = 1;         // cell-area reciprocal by verified Newton steps
   double rcp_seed = 0;              // verified_rcp_seed (0: every spacing pair not exact)
+  int nan_free = 0;                 // no height of `host` is NaN: scanned at create, kept by
+                                    // every write of the mirror (gbp_patch::nan_free_after);
+                                    // launches read it through nan_free_now
+  int64_t opt_nan_tests = 0;        // GBP_OPT_NAN_TESTS: 1 = the general state check always
   double fragile_eps = gbp::FRAGILE_EPS;  // GBP_OPT_FRAGILE_EPS (>= the default)
   int64_t opt_xcd_map = 0;          // persistent kernel: slices numbered XCD-major
   int opt_nn_stats = 0;             // 1: the matrix-core NN search counts its fp64 re-checks
@@ -82,6 +86,13 @@ inline const gbp_host::Terrain *host_mirror(gbp_terrain *t) {
   if (!t->pending.empty() && gbp_internal_mirror_sync(t) != GBP_OK) return nullptr;
   return &t->host;
 }
+
+// The map the device holds has no NaN height (GBP_OPT_NAN_FREE): true of the
+// mirror, and the mirror is up to date.  gbp_terrain_update_dev writes values
+// the host has not seen, so from that call until the mirror takes them in
+// (host_mirror, gbp_terrain_read_host) this reads 0; no read-back is added to
+// the update for it.
+inline bool nan_free_now(const gbp_terrain *t) { return t->nan_free && t->pending.empty(); }
 
 #define HIPCHK(expr)                      \
   do {                                    \

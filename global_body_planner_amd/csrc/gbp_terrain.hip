@@ -272,6 +272,7 @@ __attribute__((visibility("hidden"))) int gbp_internal_mirror_sync(gbp_terrain *
   if ((rc = read_rect(t, u, 0, h.data()))) return rc;
   // the read-back is x-major with ld = u.ny
   gbp_patch::scatter(t->host.z.data(), t->nx, t->ny, u, GBP_SRC_F64_XMAJOR, u.ny, h.data(), false);
+  t->nan_free = gbp_patch::nan_free_after(t->host.z.data(), t->nx, t->ny, u, t->nan_free != 0);
   for (auto &p : t->pending) (void)hipEventDestroy(p.done);
   t->pending.clear();
   return GBP_OK;
@@ -355,6 +356,7 @@ int gbp_terrain_update_host(gbp_terrain *t, const gbp_rect *r, int src_layout, i
   HIPCHK(hipStreamSynchronize(st));
   gbp_patch::scatter(t->host.z.data(), t->nx, t->ny, q, src_layout, ld, z,
                      t->storage == GBP_STORAGE_F32);
+  t->nan_free = gbp_patch::nan_free_after(t->host.z.data(), t->nx, t->ny, q, t->nan_free != 0);
   return GBP_OK;
 }
 
@@ -365,7 +367,9 @@ int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z
   if (rc) return rc;
   if ((copy != 0 && copy != 1) || !z) return GBP_E_INVALID_ARG;
   DeviceGuard g(t->device);
-  if ((rc = wait_pending(t))) return rc;
+  // a synchronous read: the mirror takes the pending updates in on the way
+  // (one more copy of their rectangles), which re-establishes nan_free
+  if ((rc = gbp_internal_mirror_sync(t))) return rc;
   return read_rect(t, q, copy, z);
 }
 

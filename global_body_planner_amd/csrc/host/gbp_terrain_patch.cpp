@@ -76,4 +76,17 @@ void scatter(double *mirror, int NX, int NY, const Rect &r, int layout, int64_t 
     }
 }
 
+bool nan_free(const double *z, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (std::isnan(z[i])) return false;
+  return true;
+}
+
+bool nan_free_after(const double *mirror, int NX, int NY, const Rect &r, bool was) {
+  if (!was) return nan_free(mirror, (size_t)NX * (size_t)NY);
+  for (int ix = r.ix0; ix < r.ix0 + r.nx; ix++)
+    if (!nan_free(mirror + (int64_t)ix * NY + r.iy0, (size_t)r.ny)) return false;
+  return true;
+}
+
 }  // namespace gbp_patch

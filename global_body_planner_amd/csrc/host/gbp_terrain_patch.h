@@ -6,6 +6,7 @@
 // device, and tests/native/terrain_patch_probe.cpp runs these under sanitizers.
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 
 #include "gbp.h"
@@ -64,5 +65,15 @@ int check_patch(int NX, int NY, int storage, const gbp_rect *r, int layout, int6
 // float when the handle stores fp32 (what the device then holds)
 void scatter(double *mirror, int NX, int NY, const Rect &r, int layout, int64_t ld,
              const void *src, bool f32);
+
+// none of z[0, n) is NaN (infinities are heights like any other)
+bool nan_free(const double *z, size_t n);
+
+// The same fact about the mirror once a scatter has written rectangle r, given
+// what held before it (`was`): a rectangle of non-NaN values written into a
+// NaN-free map keeps it, and reading the rectangle decides; otherwise the
+// whole mirror is scanned (a NaN written clears it; the values written may
+// have replaced the last NaN).
+bool nan_free_after(const double *mirror, int NX, int NY, const Rect &r, bool was);
 
 }  // namespace gbp_patch

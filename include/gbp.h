@@ -216,6 +216,16 @@ int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z
 #define GBP_OPT_REFILL_WINDOW 19 /* read-only, always 0: the persistent validate kernel's
                                     LDS prefetch window is retired; rows are
                                     prefetched into registers where they fit            */
+#define GBP_OPT_NAN_FREE     21  /* read-only: 1 = the host has verified that no height
+                                    of the map is NaN (at create, kept by every
+                                    gbp_terrain_update_host), so the persistent validate
+                                    kernel runs the state check without its NaN tests
+                                    and centre lookup: same results.  0 from a
+                                    gbp_terrain_update_dev until the host copy has taken
+                                    its values in (the next host re-decision or
+                                    gbp_terrain_read_host)                             */
+#define GBP_OPT_NAN_TESTS    22  /* 1: always run the general state check, whatever
+                                    GBP_OPT_NAN_FREE reads (A/B runs, tests); default 0 */
 #define GBP_KERNEL_DIRECT     0  /* one lane per attempt                              */
 #define GBP_KERNEL_PERSISTENT 1  /* persistent waves, lanes re-packed per sample      */
 int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value);
