@@ -33,6 +33,7 @@ PLAN_HALT_STAR, PLAN_HALT_STAR_PAIRS = 8, 16
 KERNEL_DIRECT, KERNEL_PERSISTENT = 0, 1
 SRC_F64_XMAJOR, SRC_F32_GRIDMAP = 0, 1
 E_INVALID_ARG, E_BAD_HANDLE, E_SHAPE, E_UNSUPPORTED = -1, -2, -5, -7
+PATH_E_CHAIN, PATH_E_SHORT = 1, 2
 
 EXPORTS = [
     "gbp_version", "gbp_status_string", "gbp_device_count", "gbp_device_alloc",
@@ -65,6 +66,9 @@ EXPORTS = [
     "gbp_plan_status_read", "gbp_plan_resolve_host", "gbp_extend_tree_dev",
     "gbp_extend_tree_finish_dev", "gbp_extend_tree_host", "gbp_tree_nearest_dev",
     "gbp_shortcut_table_dev", "gbp_shortcut_paths_host",
+    "gbp_plan_shared_read_host", "gbp_plan_shared_load_host", "gbp_plan_shared_remap_dev",
+    "gbp_tree_path_dev", "gbp_tree_path_host",
+    "gbp_tree_revalidate_keep_host", "gbp_tree_reroot_keep_host",
 ]
 
 
@@ -93,6 +97,20 @@ class RerootStats(ctypes.Structure):
     _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
                 ("n_outside", ctypes.c_int64), ("n_edge_invalid", ctypes.c_int64),
                 ("n_inherited", ctypes.c_int64), ("depth", ctypes.c_int64)]
+
+
+class SharedStats(ctypes.Structure):
+    """gbp_shared_stats (include/gbp.h): RRT*'s kept connections through a remap."""
+    _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
+                ("n_dropped_a", ctypes.c_int64), ("n_dropped_b", ctypes.c_int64),
+                ("error", ctypes.c_int64)]
+
+
+class PathInfo(ctypes.Structure):
+    """gbp_path_info (include/gbp.h): a joined path's sizes, error and length."""
+    _fields_ = [("n_states", ctypes.c_int32), ("n_from_a", ctypes.c_int32),
+                ("n_from_b", ctypes.c_int32), ("error", ctypes.c_int32),
+                ("length", ctypes.c_double)]
 
 
 def sampling(state_flag=False, state_p=0.05, speed_direction=False, action_flag=False,
@@ -189,6 +207,8 @@ def load(path=None):
         "gbp_tree_reroot_dev": (I, [P, I64, ctypes.c_int32, P, P, P, P]),
         "gbp_tree_reroot_host": (I, [P, P, ctypes.c_int32, I, I, P, P, P]),
         "gbp_tree_reroot_last": (I, [P, P]),
+        "gbp_tree_revalidate_keep_host": (I, [P, P, I, I, P, P, I64, P, P]),
+        "gbp_tree_reroot_keep_host": (I, [P, P, ctypes.c_int32, I, I, P, P, I64, P, P]),
         "gbp_plan_ws_create": (I, [P, I64, P]),
         "gbp_plan_ws_destroy": (I, [P]),
         "gbp_plan_reset": (I, [P, I64, P]),
@@ -207,6 +227,11 @@ def load(path=None):
         "gbp_shortcut_table_dev": (I, [P, I64, P, P, I, P, P, P]),
         "gbp_shortcut_paths_host": (I, [P, I64, P, P, P, I, I, ctypes.c_double, ctypes.c_double,
                                         P, P, P, P, P, P, P]),
+        "gbp_plan_shared_read_host": (I, [P, I64, P, P, P, P, P, P]),
+        "gbp_plan_shared_load_host": (I, [P, P, P, I64, P, P]),
+        "gbp_plan_shared_remap_dev": (I, [P, P, P, P, I64, P, I64, P, P]),
+        "gbp_tree_path_dev": (I, [P, ctypes.c_int32, P, ctypes.c_int32, P, I64, P, P, P, P]),
+        "gbp_tree_path_host": (I, [P, ctypes.c_int32, P, ctypes.c_int32, P, I64, P, P, P, P]),
         "gbp_nearest_batch_dev": (I, [I64, P, I64, P, P, P, P]),
         "gbp_nearest_batch_host": (I, [I64, P, I64, P, P, P]),
         "gbp_neighbors_batch_dev": (I, [I64, P, I64, P, ctypes.c_double, I, P, P, P]),

@@ -1,7 +1,9 @@
 // gbp_internal.h — definitions shared by the engine's translation units
 // (gbp_engine.hip: terrain, lookups, pair checks, samplers, extend, NN;
 // gbp_plan.hip: device trees and the device-resident planner loop;
-// gbp_terrain.hip: a handle's heights updated in place and its host mirror).
+// gbp_terrain.hip: a handle's heights updated in place and its host mirror;
+// gbp_replan.hip: RRT*'s kept connections carried between searches and the
+// joined path of two device trees).
 // Not part of the C ABI.
 #pragma once
 
@@ -211,6 +213,177 @@ int stage_buf(DevBuf &b, F carve) {
   }
   return stage_carve(b.p, need, carve);
 }
+
+// ============================================================================
+// the planner's handles (gbp_plan.hip creates, fills and frees them;
+// gbp_replan.hip reads the trees and the kept connections)
+// ============================================================================
+struct gbp_tree {
+  int device = 0;
+  int64_t cap = 0;
+  double *v = nullptr;        // [cap][8] vertex states (GraphClass vertices)
+  _Float16 *vh = nullptr;     // [cap][NH_ROW] fp16 split rows (matrix-core search, nn_put_hrow)
+  float *hm = nullptr;        // [16]: [0, 8) max |64 v[j][k]|, [8] (bits) 1 = a row outside fp16
+  double *a = nullptr;        // [cap][10] the action that reached each vertex
+  double *g = nullptr;        // [cap] cost to come: g[parent] + poseDistance
+  int32_t *parent = nullptr;  // [cap], -1 at the root
+  // successor lists (graph_class.cpp:28-58 successors_), first child / next
+  // sibling: the RRT*-Connect rewiring updates g over a rewired vertex's
+  // subtree (graph_class.cpp:131-138); kept by every append (child order is
+  // immaterial: a child's g depends on its parent's alone)
+  int32_t *child = nullptr, *sibling = nullptr;  // [cap], -1 = none
+  int32_t *prev = nullptr;    // [cap] previous sibling (-1: first child): O(1) removeEdge
+  int32_t *bfs = nullptr;     // [2 cap] scratch: the subtree update's two level queues
+  int32_t *count = nullptr;   // [1] number of vertices (device resident)
+  // gbp_tree_revalidate_dev's attempt rows (grow-only; kernels do not read these two)
+  void *rv = nullptr;
+  size_t rv_bytes = 0;
+};
+
+// the segment scans k_nn_hreduce lists (a fourth unit of a segment within
+// the threshold: the segment's rows in fp64) and their merge; one set for the
+// caller's stream, one for the look-ahead stream
+constexpr int NSC_CAP = 16384;  // listed scans per search (more: scanned in the reduce)
+constexpr int NSC_UNITS = NSC_CAP * 8;  // (scan, part) results: NSC_CAP x NSC_P
+struct NsBuf {
+  uint32_t cap;             // list capacity (NSC_CAP; GBP_NSC_CAP lowers it: tests)
+  int2 *list;               // (query, segment)
+  uint32_t *cnt;            // listed
+  double *ed;               // [NSC_UNITS] a scan part's minimum
+  int32_t *ei;              // ... its index (lowest at that minimum)
+  double *hd;               // [bmax] the reduce's own answer
+  int32_t *hi;
+  int2 *qh;                 // [bmax] a query's first entry and its entries
+};
+
+// the look-ahead search's device state (gbp_plan_ws::la), by half % 3 (the
+// drawn-ahead target sets) and by parity (the searched trees' snapshots)
+struct gbp_plan_la {
+  int32_t nt[3];     // valid targets drawn for the half (ordered_rank's total)
+  uint32_t frag[3];  // half + 1 when one of its draws was FRAGILE
+  int32_t nv[2];     // the searched tree's vertex count when its search was launched
+  uint32_t go[2];    // 0: the sequence had stopped when the search was launched (it idles)
+};
+
+struct gbp_plan_ws {
+  int device = 0;
+  int num_cus = 256;
+  int64_t bmax = 0;            // largest batch of draws per half-iteration
+  gbp_plan_status *st = nullptr;
+  unsigned long long *tiles = nullptr;  // look-back tile states
+  uint32_t epoch = 0;          // per-compaction tag of the tile states
+  uint64_t seq = 0;            // launch sequence number of the planner kernels (gated())
+  int nn_stats = 0;            // GBP_OPT_NN_STATS: k_nn_hreduce counts its re-checks in the status
+  int nn_items = 4096;         // matrix-core search: work items (= waves) per launch
+  int64_t ntiles = 0;
+  // stage 0-1: three sets, by half % 3 (with the look-ahead search, half
+  // h + 2's targets are drawn while half h + 1's are searched and half h
+  // still reads its own); cand..tqh point at the set of the half being
+  // enqueued or resolved (select_targets)
+  struct TargetSet {
+    double *cand, *targets;
+    uint32_t *cflag;
+    _Float16 *tqh;
+  } tset[3] = {};
+  double *cand = nullptr;      // [bmax][8] drawn states
+  uint32_t *cflag = nullptr;   // [bmax] their isValidState flags
+  double *targets = nullptr;   // [bmax][8] the valid ones, in draw order
+  _Float16 *tqh = nullptr;     // [bmax][NH_ROW] their fp16 rows (k_nn_mfma's queries)
+  // stage 2-3; nn, cs and ca in two sets by the half's parity (the
+  // look-ahead search of half h + 1 writes its own while half h reads)
+  int32_t *nn = nullptr;       // [bmax] nearest vertex of T per target
+  double *cs = nullptr;        // [6 bmax][8] candidate s_near
+  double *ca = nullptr;        // [6 bmax][10] candidate actions
+  int32_t *nnp[2] = {};
+  double *csp[2] = {}, *cap[2] = {};
+  double *csn = nullptr;       // [6 bmax][8] candidate s_new
+  uint32_t *cf = nullptr;      // [6 bmax] candidate flags
+  uint32_t *cc = nullptr;      // [6 bmax] candidate counts
+  int32_t *eres = nullptr;     // [bmax] extend result
+  int32_t *echo = nullptr;     // [bmax] chosen candidate
+  double *esn = nullptr;       // [bmax][8]
+  double *ean = nullptr;       // [bmax][10]
+  uint32_t *ef = nullptr;      // [bmax] extend flags
+  int32_t *evtx = nullptr;     // [bmax] new vertex index (or -1)
+  // stage 4-5
+  int32_t *nno = nullptr;      // [bmax] nearest vertex of O per new vertex
+  int32_t *kres = nullptr;     // [bmax] connect result
+  double *ksn = nullptr;       // [bmax][8]
+  double *kan = nullptr;       // [bmax][10]
+  uint32_t *kf = nullptr;      // [bmax] connect flags
+  // nearest-neighbour partials: NN_MAX_CHUNKS * bmax slots, pd[c * nq + qi]
+  // (nn_d2 / nn_i2: the look-ahead search's, on its own stream)
+  double *nn_d = nullptr, *nn_d2 = nullptr;
+  int32_t *nn_i = nullptr, *nn_i2 = nullptr;
+  // the direct search for a few queries (k_nn_small): per-workgroup partials
+  // and the completion count of its last-workgroup reduce
+  double *ns_d = nullptr;
+  int32_t *ns_i = nullptr;
+  uint32_t *ns_fin = nullptr;
+  int ns_grid = 1;             // its workgroups (one per CU of an XCD)
+  int64_t ns_capq = 0;         // queries its partials hold (ns_grid x ns_capq slots)
+  NsBuf nsb[2] = {};           // k_nn_scan's lists: the caller's stream, the look-ahead's
+  // the look-ahead search (gbp_plan_halves_dev): half h + 1's targets drawn
+  // and searched on la_stream while half h's extends, connects and appends
+  // run on the caller's stream (la_go: main -> side, la_done: side -> main)
+  gbp_plan_la *la = nullptr;   // device: counts, snapshots, flags
+  unsigned long long *la_tiles = nullptr;  // look-back tiles of the drawn-ahead targets
+  hipStream_t la_stream = nullptr;
+  hipEvent_t la_go = nullptr, la_done = nullptr;
+  void *block = nullptr;       // the one allocation all of the above live in
+  // RRT*-Connect (gbp_plan_star_config; star = 0: RRT-Connect): stages 6-7
+  int star = 0;
+  double star_delta = 3.0;     // rrt_star_connect.h:59
+  int64_t star_max_pairs = 0, star_max_shared = 0;
+  int64_t star_items = 0;      // scan items per half (new vertex x position chunk)
+  int star_grid = 0;           // count / fill / check workgroups cap (GBP_STAR_GRID, tests; 0: none)
+  int64_t star_ch = 1024;      // map positions per scan item before growth (STAR_CH)
+  int32_t star_lds[3] = {-1, -1, -1};  // the replay's LDS limits (GBP_STAR_LDS, tests; -1: RP, RK, RQ)
+  // a half's insertion buffers, one set per tree (half & 1): half h's replay
+  // runs on star_stream beside half h's connects and half h + 1, which fills
+  // the other set; half h + 2 refills this one only after the replay (its
+  // stage 5 waits for it first)
+  struct StarSet {
+    unsigned long long *scnt = nullptr;  // [star_items] neighbours per scan item (k_star_count: tile_word)
+    int32_t *sioff = nullptr;    // [star_items] the items' offsets
+    int32_t *soff = nullptr;     // [bmax + 1] each new vertex's first pair
+    int32_t *snb = nullptr;      // [max_pairs] the neighbour of each pair
+    int32_t *sown = nullptr;     // [max_pairs] its new vertex (k)
+    int32_t *srowof = nullptr;   // [2 max_pairs] connect check -> pair-check row (-1: none)
+    double *srs = nullptr;       // [2 max_pairs][8] rows: the pair checks' states
+    double *sra = nullptr;       // [2 max_pairs][10] and actions
+    uint32_t *srf = nullptr;     // [2 max_pairs] their flags
+    int64_t *meta = nullptr;     // [4] n_added, added_base, pairs (k_star_count's scan); shared count (stage-5 append)
+    uint32_t *sfin = nullptr;    // [64] k_star_count's finished-workgroup count (zeroed, self-resetting)
+  } ss[2];
+  int32_t *kvtx = nullptr;     // [bmax] O's vertex of each connection (-1: none)
+  // the replay (and the best connection's ranking) off the caller's stream:
+  // e6 (stage 6 done) and e5 (stage 5 done) main -> star, rdone[k] star -> main
+  // (tree k's last replay / ranking), sdone the call's join
+  hipStream_t star_stream = nullptr;
+  hipEvent_t star_e6 = nullptr, star_e5 = nullptr, star_rdone[2] = {nullptr, nullptr},
+             star_sdone = nullptr;
+  // gbp_plan_stage_timing: a ring of per-half timing events (start, after
+  // stage 3, after stage 6, replay start / end, end), read back once complete
+  bool timing = false;
+  struct TimedHalf {
+    hipEvent_t ev[8] = {};  // + [6] after stage 6's connect actions, [7] after their pair checks
+    bool pending = false, star = false;
+    int32_t half = 0;
+  };
+  TimedHalf *tring = nullptr;  // [ntring] (a plain array: no template of a gbp type exported)
+  size_t ntring = 0, tnext = 0;
+  double tsum[7] = {0, 0, 0, 0, 0, 0, 0};
+  int64_t tcount = 0;
+  int32_t *sshared = nullptr;  // [max_shared][2] the REACHED connections (a, b)
+  void *star_block = nullptr;
+  // gbp_replan.hip's scratch (the list's second buffer, the compaction's tile
+  // counts and offsets, its control record): grow-only, sized by
+  // star_max_shared when an entry first needs it; host side only, no kernel
+  // of gbp_plan.hip takes it
+  void *replan = nullptr;
+  size_t replan_bytes = 0;
+};
 
 // the device's look-ahead stream of the planner loop (created once per
 // process and device; null on failure); gbp_plan.hip

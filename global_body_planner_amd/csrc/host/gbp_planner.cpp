@@ -16,6 +16,7 @@
 #include <cstring>
 #include <climits>
 #include <fstream>
+#include <memory>
 #include <numeric>
 #include <sstream>
 
@@ -1588,6 +1589,13 @@ void open_search(DeviceSearch &S, int dev, const BatchStats &st, const State &s_
   S.half = S.half0 = (int32_t)st.warm_half;
   if (st.warm_n[0] > 0 || st.warm_n[1] > 0 || S.half0 > 0) extend_counter = st.warm_extend;
   chk(gbp_plan_reset(S.ws, extend_counter, S.stream), "plan reset");
+  // the continuation's kept connections, ranked with the warm trees' g
+  if (st.warm_shared_n < 0 || (st.warm_shared_n > 0 && (!S.star || !st.warm_shared)))
+    throw EngineError(GBP_E_INVALID_ARG, "warm start: kept connections");
+  if (st.warm_shared_n > 0)
+    chk(gbp_plan_shared_load_host(S.ws, S.tree[0], S.tree[1], st.warm_shared_n, st.warm_shared,
+                                  S.stream),
+        "warm start: kept connections");
   S.g_max = (int)std::max<int64_t>(2, std::min<int64_t>(64, (1 << 21) / S.batch)) & ~1;
 }
 
@@ -1676,6 +1684,16 @@ void close_search(DeviceSearch &S, BatchStats &st, HostTree &A, HostTree &B) {
       st.dump->g[k] = t[k]->g;
     }
   }
+}
+
+// RRT*'s kept connections in list order (S.ps is the current status)
+void read_shared(DeviceSearch &S, std::vector<std::array<int32_t, 2>> &pairs) {
+  pairs.assign((size_t)std::max<int32_t>(S.ps.n_shared, 0), {-1, -1});
+  int64_t n = 0;
+  chk(gbp_plan_shared_read_host(S.ws, (int64_t)pairs.size(), pairs.empty() ? nullptr : pairs[0].data(),
+                                &n, nullptr, nullptr, nullptr, S.stream),
+      "kept connections");
+  if (n != (int64_t)pairs.size()) throw EngineError(GBP_E_SHAPE, "kept connections: stale status");
 }
 
 }  // namespace
@@ -2159,6 +2177,7 @@ bool RRTStarConnectClass::buildRRTStarConnectDevice(FastTerrainMap &terrain, Sta
   st.connects += ps.stat_star_connects;
   st.rewires += ps.stat_rewires;
   st.solutions += ps.n_shared;
+  if (st.shared_dump) read_shared(S, *st.shared_dump);
   HostTree A, B;
   close_search(S, st, A, B);
   num_vertices = (int)(A.v.size() + B.v.size());
@@ -2170,6 +2189,265 @@ bool RRTStarConnectClass::buildRRTStarConnectDevice(FastTerrainMap &terrain, Sta
   reportPath(joinTreePaths(A.view(), ps.best_a, B.view(), ps.best_b), state_sequence,
              action_sequence);
   return true;
+}
+
+// ---- ReplanSession (include/gbp_planner.h) ------------------------------------
+struct ReplanSession::Impl {
+  DeviceSearch S;
+  int device = 0;
+  DeviceBuffer remap[2];   // the last prune's / re-root's device remaps (int32)
+  DeviceBuffer stats;      // gbp_shared_stats[1]
+  int64_t path_cap = 256;  // rows bestPath asks for first (grown to the length needed)
+  ~Impl() {
+    if (S.stream) gbp_stream_synchronize(S.stream);  // before the buffers go
+  }
+};
+
+ReplanSession::ReplanSession() = default;
+ReplanSession::~ReplanSession() { end(); }
+
+void ReplanSession::end() {
+  delete impl_;
+  impl_ = nullptr;
+}
+
+ReplanSession::Impl &ReplanSession::impl() const {
+  if (!impl_) throw EngineError(GBP_E_BAD_HANDLE, "ReplanSession: begin was not called");
+  return *impl_;
+}
+
+int32_t ReplanSession::nextHalf() const { return impl().S.half; }
+int64_t ReplanSession::extendCounter() const { return impl().S.ps.ext_counter; }
+
+void ReplanSession::begin(FastTerrainMap &terrain, State s_start, State s_goal, int batch,
+                          double delta, uint64_t seed) {
+  end();
+  setSeed(seed);
+  goal_found = false;
+  wall_to_first_ = -1;
+  rewires_ = 0;
+  extend_counter_ = 0;
+  best_cost_ = INFINITY_COST;
+  cost_vector_.clear();
+  cost_vector_times_.clear();
+  gbp_sampling cfg = samplingConfig();  // as buildRRTStarConnectDevice: plain randomState targets
+  cfg.state_flag = 0;
+  chk(gbp_terrain_set_sampling(terrain.handle(), &cfg), "sampling");
+  std::unique_ptr<Impl> I(new Impl);
+  I->device = terrain.device();
+  DeviceSearch &S = I->S;
+  S.h = terrain.handle();
+  S.batch = batch;
+  S.adaptive = state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0;
+  S.seed = seed_;
+  S.tstream[0] = 401;
+  S.tstream[1] = 402;
+  S.star = true;
+  S.star_delta = delta;
+  const BatchStats none;
+  open_search(S, terrain.device(), none, s_start, s_goal, extend_counter_);
+  I->stats.reserve(terrain.device(), 1, sizeof(gbp_shared_stats), 1, "ReplanSession: stats");
+  chk(gbp_plan_status_read(S.ws, &S.ps, S.stream), "plan status");
+  impl_ = I.release();
+}
+
+bool ReplanSession::search(double max_time, int64_t max_halves, BatchStats *stats) {
+  DeviceSearch &S = impl().S;
+  const Stopwatch clk;
+  BatchStats local;
+  BatchStats &st = stats ? *stats : local;
+  const gbp_plan_status &ps = S.ps;
+  const int32_t h0 = S.half;
+  while (clk.seconds() < max_time && (max_halves <= 0 || S.half - h0 + 2 <= max_halves)) {
+    if (max_halves > 0)
+      S.group = (int)std::min<int64_t>(S.group, (max_halves - (S.half - h0)) & ~1LL);
+    run_group(S, st);
+    if (ps.n_shared > 0 && !goal_found) {
+      goal_found = true;
+      elapsed_to_first = clk.elapsed();
+      wall_to_first_ = elapsed_to_first.count();
+    }
+    if (ps.best_a >= 0 && (cost_vector_.empty() || ps.best_cost < cost_vector_.back())) {
+      cost_vector_.push_back(ps.best_cost);  // the best so far, once per group (as the build)
+      cost_vector_times_.push_back(clk.seconds());
+    }
+    S.group = std::min(S.group * 2, S.g_max);
+  }
+  extend_counter_ = ps.ext_counter;
+  rewires_ = ps.stat_rewires;
+  best_cost_ = ps.best_a >= 0 ? ps.best_cost : INFINITY_COST;
+  // this call's halves are added; the counters below are set to the session's
+  // totals so far (include/gbp_planner.h)
+  st.halves += S.half - h0;
+  st.iterations += (S.half - h0) / 2;
+  st.rewires = ps.stat_rewires;
+  st.solutions = ps.n_shared;
+  st.targets = st.extends = ps.stat_targets;
+  st.attempts_checked = ps.stat_attempts;
+  st.connects = ps.stat_added + ps.stat_star_connects;
+  st.fragile_resolved = ps.stat_fragile_resolved;
+  st.depth_capped = ps.stat_depth_capped;
+  st.vertices_a = S.known[0];
+  st.vertices_b = S.known[1];
+  st.meet_a = ps.best_a;
+  st.meet_b = ps.best_b;
+  num_vertices = (int)(S.known[0] + S.known[1]);
+  if (st.dump) dump(*st.dump);
+  if (st.shared_dump) read_shared(S, *st.shared_dump);
+  return ps.best_a >= 0;
+}
+
+// the list through the remaps the last prune / re-root left in I.remap (false:
+// that tree did not change), then the status as it now stands
+void ReplanSession::carryShared(bool remap_a, bool remap_b, const int64_t n_before[2],
+                                SharedStats *shared) {
+  Impl &I = impl();
+  DeviceSearch &S = I.S;
+  chk(gbp_plan_shared_remap_dev(S.ws, S.tree[0], S.tree[1],
+                                remap_a ? I.remap[0].data<int32_t>() : nullptr, n_before[0],
+                                remap_b ? I.remap[1].data<int32_t>() : nullptr, n_before[1],
+                                I.stats.data<gbp_shared_stats>(), S.stream),
+      "kept connections: remap");
+  gbp_shared_stats hs{};
+  chk(gbp_memcpy_d2h(&hs, I.stats.data<void>(), sizeof hs, S.stream), "kept connections: stats");
+  chk(gbp_plan_status_read(S.ws, &S.ps, S.stream), "plan status");  // synchronises
+  if (hs.error) throw EngineError(GBP_E_INVALID_ARG, "kept connections: an index outside its tree");
+  best_cost_ = S.ps.best_a >= 0 ? S.ps.best_cost : INFINITY_COST;
+  // a carry may raise the best (its pair dropped, or g derived again): the
+  // history records what the session holds now
+  if (S.ps.best_a >= 0 && (cost_vector_.empty() || S.ps.best_cost != cost_vector_.back())) {
+    cost_vector_.push_back(S.ps.best_cost);
+    cost_vector_times_.push_back(0.0);
+  }
+  if (shared) {
+    shared->n_before = hs.n_before;
+    shared->n_kept = hs.n_kept;
+    shared->n_dropped_a = hs.n_dropped_a;
+    shared->n_dropped_b = hs.n_dropped_b;
+  }
+}
+
+void ReplanSession::mapChanged(FastTerrainMap &terrain, PruneStats stats[2], SharedStats *shared) {
+  Impl &I = impl();
+  DeviceSearch &S = I.S;
+  if (terrain.handle() != S.h)
+    throw EngineError(GBP_E_INVALID_ARG, "ReplanSession: not the terrain the session began on");
+  // the tree entries run on the terrain's own stream
+  chk(gbp_stream_synchronize(S.stream), "stream");
+  const int64_t before[2] = {S.known[0], S.known[1]};
+  for (int k = 0; k < 2; k++)
+    I.remap[k].reserve(terrain.device(), before[k], sizeof(int32_t), 1 << 12, "ReplanSession: remap");
+  for (int k = 0; k < 2; k++) {
+    gbp_prune_stats ps{};
+    PruneStats done;
+    chk(gbp_tree_revalidate_keep_host(S.h, S.tree[k], k == 0 ? FORWARD : REVERSE, S.adaptive, nullptr,
+                                      I.remap[k].data<int32_t>(), I.remap[k].capacity(), &ps,
+                                      &done.fragile_resolved),
+        "ReplanSession: prune");
+    done.n_before = ps.n_before;
+    done.n_kept = ps.n_kept;
+    done.n_edge_invalid = ps.n_edge_invalid;
+    done.n_inherited = ps.n_inherited;
+    S.known[k] = ps.n_kept;
+    if (stats) stats[k] = done;
+  }
+  carryShared(true, true, before, shared);
+}
+
+void ReplanSession::robotAt(int32_t vertex, RerootStats &stats, SharedStats *shared,
+                            bool test_edges) {
+  Impl &I = impl();
+  DeviceSearch &S = I.S;
+  chk(gbp_stream_synchronize(S.stream), "stream");
+  const int64_t before[2] = {S.known[0], S.known[1]};
+  I.remap[0].reserve(I.device, before[0], sizeof(int32_t), 1 << 12, "ReplanSession: remap");
+  gbp_reroot_stats rs{};
+  RerootStats done;
+  chk(gbp_tree_reroot_keep_host(test_edges ? S.h : nullptr, S.tree[0], vertex, FORWARD, S.adaptive,
+                                nullptr, I.remap[0].data<int32_t>(), I.remap[0].capacity(), &rs,
+                                &done.fragile_resolved),
+      "ReplanSession: re-root");
+  done.n_before = rs.n_before;
+  done.n_kept = rs.n_kept;
+  done.n_outside = rs.n_outside;
+  done.n_edge_invalid = rs.n_edge_invalid;
+  done.n_inherited = rs.n_inherited;
+  done.depth = rs.depth;
+  S.known[0] = rs.n_kept;
+  stats = done;
+  carryShared(true, false, before, shared);
+}
+
+void ReplanSession::robotAt(const State &s, RerootStats &stats, SharedStats *shared,
+                            bool test_edges) {
+  Impl &I = impl();
+  DeviceSearch &S = I.S;
+  // the start-tree vertices of the current best path: its first n_from_a
+  // states, and the chain root -> best_a from the parents alone
+  std::vector<State> states;
+  std::vector<Action> actions;
+  if (!bestPath(states, actions))
+    throw EngineError(GBP_E_INVALID_ARG, "ReplanSession: no path to locate the robot on");
+  std::vector<int32_t> parent((size_t)S.known[0]);
+  chk(gbp_tree_read(S.tree[0], 0, S.known[0], nullptr, nullptr, parent.data(), nullptr, S.stream),
+      "ReplanSession: parents");
+  const std::vector<int> chain = startTreePath(parent, S.ps.best_a);
+  int32_t vertex = -1;
+  for (size_t k = 0; k < chain.size() && k < states.size() && vertex < 0; k++)
+    if (std::memcmp(states[k].data(), s.data(), sizeof(State)) == 0) vertex = chain[k];
+  if (vertex < 0)
+    throw EngineError(GBP_E_INVALID_ARG, "ReplanSession: the state is no start-tree vertex of the path");
+  robotAt(vertex, stats, shared, test_edges);
+}
+
+bool ReplanSession::bestPath(std::vector<State> &state_sequence,
+                             std::vector<Action> &action_sequence) {
+  Impl &I = impl();
+  DeviceSearch &S = I.S;
+  if (S.ps.best_a < 0 || S.ps.best_b < 0) return false;
+  std::vector<State> states;
+  std::vector<Action> actions;
+  gbp_path_info info{};
+  for (int attempt = 0; attempt < 2; attempt++) {
+    states.resize((size_t)I.path_cap);
+    actions.resize((size_t)I.path_cap);
+    chk(gbp_tree_path_host(S.tree[0], -1, S.tree[1], -1, S.ws, I.path_cap, states[0].data(),
+                           actions[0].data(), &info, S.stream),
+        "ReplanSession: path");
+    if (info.error != GBP_PATH_E_SHORT) break;
+    I.path_cap = info.n_states;  // the length needed: once more
+  }
+  if (info.error) throw EngineError(GBP_E_SHAPE, "ReplanSession: the trees' parents are no chains");
+  if (info.n_states < 1) return false;
+  State s_ib;  // the yaw sum of the goal tree's chain ends at best_b's own state
+  chk(gbp_tree_read(S.tree[1], S.ps.best_b, 1, s_ib.data(), nullptr, nullptr, nullptr, S.stream),
+      "ReplanSession: path end");
+  states.resize((size_t)info.n_states);
+  actions.resize((size_t)info.n_states - 1);
+  JoinedPath p = pathFromRows(std::move(states), std::move(actions), info.n_from_a, s_ib, info.length);
+  if (p.states.empty()) throw EngineError(GBP_E_SHAPE, "ReplanSession: path rows");
+  reportPath(std::move(p), state_sequence, action_sequence);
+  return true;
+}
+
+void ReplanSession::dump(TreeDump &trees) {
+  DeviceSearch &S = impl().S;
+  for (int k = 0; k < 2; k++) {
+    HostTree h;
+    read_tree(S.tree[k], S.stream, h);
+    trees.v[k] = std::move(h.v);
+    trees.a[k] = std::move(h.a);
+    trees.parent[k] = std::move(h.parent);
+    trees.g[k] = std::move(h.g);
+  }
+}
+
+void ReplanSession::sharedConnections(std::vector<std::array<int32_t, 2>> &pairs,
+                                      std::array<int32_t, 2> *best, double *best_cost) {
+  DeviceSearch &S = impl().S;
+  read_shared(S, pairs);
+  if (best) *best = {S.ps.best_a, S.ps.best_b};
+  if (best_cost) *best_cost = S.ps.best_cost;
 }
 
 }  // namespace gbp_amd

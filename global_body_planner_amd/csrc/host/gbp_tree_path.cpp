@@ -75,4 +75,24 @@ JoinedPath joinTreePaths(const TreeView &Ta, int ia, const TreeView &Tb, int ib)
   return p;
 }
 
+JoinedPath pathFromRows(std::vector<State> states, std::vector<Action> actions, int n_from_a,
+                        const State &s_ib, double length) {
+  JoinedPath p;
+  const int n = (int)states.size();
+  if (n < 1 || n_from_a < 1 || n_from_a > n || (int)actions.size() != n - 1) return p;
+  // the two chains' sums, each from its own root down, as chainYaw forms them:
+  // Ta's chain is states[0, n_from_a); Tb's runs from the path's last state
+  // back to states[n_from_a] and ends at ib's own state
+  double ya = 0, yb = 0;
+  for (int i = 1; i < n_from_a; i++) ya = ya + stateYawDistance(states[i - 1], states[i]);
+  for (int i = n - 1; i > n_from_a; i--) yb = yb + stateYawDistance(states[i], states[i - 1]);
+  if (n > n_from_a) yb = yb + stateYawDistance(states[n_from_a], s_ib);
+  p.yaw = ya + yb;
+  p.length = length;
+  p.duration = pathDuration(actions);
+  p.states = std::move(states);
+  p.actions = std::move(actions);
+  return p;
+}
+
 }  // namespace gbp_amd

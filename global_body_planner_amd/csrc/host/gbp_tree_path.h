@@ -49,4 +49,13 @@ double pathDuration(const std::vector<Action> &actions);
 // child's action (getActionSequenceReverse).
 JoinedPath joinTreePaths(const TreeView &Ta, int ia, const TreeView &Tb, int ib);
 
+// The same JoinedPath from the joined rows themselves (gbp_tree_path_host
+// gathers them on the device): the first n_from_a states are Ta's chain, the
+// rest Tb's chain below ib walked up to its root; s_ib is ib's own state,
+// which the path drops but the yaw sum of Tb's chain ends at; length = g_a[ia]
+// + g_b[ib] as the device returned it.  Yaw and duration are summed here in
+// joinTreePaths' order.  An empty path when the sizes do not fit.
+JoinedPath pathFromRows(std::vector<State> states, std::vector<Action> actions, int n_from_a,
+                        const State &s_ib, double length);
+
 }  // namespace gbp_amd

@@ -486,7 +486,7 @@ class DeviceTree:
         check(self._lib.gbp_tree_load_host(self._h, s.shape[0], _np_ptr(s), _np_ptr(a), _np_ptr(p),
                                            None), "tree_load")
 
-    def revalidate(self, terrain, direction, adaptive=False):
+    def revalidate(self, terrain, direction, adaptive=False, remap_dev=None):
         """gbp_tree_revalidate_host: prunes the tree against `terrain` (an
         engine.Terrain holding the changed map).  A vertex stays when the pair
         check of (v[parent], action, direction) holds on that terrain for every
@@ -494,19 +494,29 @@ class DeviceTree:
         (remap, stats): remap [n before] int32, a vertex's new index or -1;
         stats a dict of n_before, n_kept, n_edge_invalid (pruned vertices whose
         own edge failed), n_inherited (pruned through an ancestor only) and
-        n_resolved (FRAGILE edges re-decided on the host with glibc)."""
+        n_resolved (FRAGILE edges re-decided on the host with glibc).
+        remap_dev: an int32 device tensor of at least len(self) elements that
+        also receives the remap (gbp_tree_revalidate_keep_host), for
+        PlanWorkspace.shared_remap."""
         remap = np.empty(len(self), np.int32)
         st = L.PruneStats()
         k = ctypes.c_int64(0)
-        check(self._lib.gbp_tree_revalidate_host(terrain._h, self._h, int(direction),
-                                                 int(bool(adaptive)), _np_ptr(remap),
-                                                 ctypes.byref(st), ctypes.byref(k)),
-              "tree_revalidate")
+        if remap_dev is not None:  # gbp_tree_revalidate_keep_host: the remap stays in HBM too
+            check(self._lib.gbp_tree_revalidate_keep_host(terrain._h, self._h, int(direction),
+                                                          int(bool(adaptive)), _np_ptr(remap),
+                                                          _ptr(remap_dev), remap_dev.numel(),
+                                                          ctypes.byref(st), ctypes.byref(k)),
+                  "tree_revalidate_keep")
+        else:
+            check(self._lib.gbp_tree_revalidate_host(terrain._h, self._h, int(direction),
+                                                     int(bool(adaptive)), _np_ptr(remap),
+                                                     ctypes.byref(st), ctypes.byref(k)),
+                  "tree_revalidate")
         stats = {name: getattr(st, name) for name, _ in L.PruneStats._fields_}
         stats["n_resolved"] = k.value
         return remap, stats
 
-    def reroot(self, vertex, terrain=None, direction=L.FORWARD, adaptive=False):
+    def reroot(self, vertex, terrain=None, direction=L.FORWARD, adaptive=False, remap_dev=None):
         """gbp_tree_reroot_host: makes `vertex` the root and keeps the subtree
         below it, in HBM.  The new root becomes vertex 0 (action zeroed, parent
         -1), the other kept vertices follow in ascending old index, and g is
@@ -517,17 +527,46 @@ class DeviceTree:
         int32, a vertex's new index or -1; stats a dict of n_before, n_kept,
         n_outside (not below the new root), n_edge_invalid, n_inherited (below
         it: own edge failed / an ancestor's did), depth (most edges between
-        the new root and a kept vertex) and n_resolved."""
+        the new root and a kept vertex) and n_resolved.  remap_dev: as in
+        revalidate (gbp_tree_reroot_keep_host)."""
         remap = np.empty(len(self), np.int32)
         st = L.RerootStats()
         k = ctypes.c_int64(0)
-        check(self._lib.gbp_tree_reroot_host(terrain._h if terrain is not None else None, self._h,
-                                             int(vertex), int(direction), int(bool(adaptive)),
-                                             _np_ptr(remap), ctypes.byref(st), ctypes.byref(k)),
-              "tree_reroot")
+        th = terrain._h if terrain is not None else None
+        if remap_dev is not None:  # gbp_tree_reroot_keep_host: the remap stays in HBM too
+            check(self._lib.gbp_tree_reroot_keep_host(th, self._h, int(vertex), int(direction),
+                                                      int(bool(adaptive)), _np_ptr(remap),
+                                                      _ptr(remap_dev), remap_dev.numel(),
+                                                      ctypes.byref(st), ctypes.byref(k)),
+                  "tree_reroot_keep")
+        else:
+            check(self._lib.gbp_tree_reroot_host(th, self._h, int(vertex), int(direction),
+                                                 int(bool(adaptive)), _np_ptr(remap),
+                                                 ctypes.byref(st), ctypes.byref(k)), "tree_reroot")
         stats = {name: getattr(st, name) for name, _ in L.RerootStats._fields_}
         stats["n_resolved"] = k.value
         return remap, stats
+
+    def capacity(self):
+        c = ctypes.c_int64(0)
+        check(self._lib.gbp_tree_capacity(self._h, ctypes.byref(c)), "tree_capacity")
+        return c.value
+
+    def reserve(self, capacity):
+        check(self._lib.gbp_tree_reserve(self._h, int(capacity), None), "tree_reserve")
+
+    def read_parents(self):
+        """parents [n] int32 alone (4 of a vertex's 156 bytes)."""
+        p = np.empty(len(self), np.int32)
+        check(self._lib.gbp_tree_read(self._h, 0, p.size, None, None, _np_ptr(p), None, None),
+              "tree_read")
+        return p
+
+    def read_state(self, i):
+        s = np.empty(8)
+        check(self._lib.gbp_tree_read(self._h, int(i), 1, _np_ptr(s), None, None, None, None),
+              "tree_read")
+        return s
 
     def read(self):
         """(states [n][8], actions [n][10], parents [n], g [n]) numpy."""
@@ -591,8 +630,17 @@ class PlanWorkspace:
         check(self._lib.gbp_plan_status_read(self._h, ctypes.byref(st), _stream(device)), "status")
         return {k: getattr(st, k) for k, _ in PlanStatus._fields_}
 
-    def reset(self, device=0):
-        check(self._lib.gbp_plan_reset(self._h, 0, _stream(device)), "plan_reset")
+    def reset(self, device=0, extend_counter=0):
+        check(self._lib.gbp_plan_reset(self._h, int(extend_counter), _stream(device)), "plan_reset")
+
+    def resolve(self, terrain, tree, other, direction, batch, adaptive=False, device=0):
+        """gbp_plan_resolve_host: the halted stage's FRAGILE items re-decided
+        with glibc; (stage to resume the halted half at, items re-decided)."""
+        resume, nres = ctypes.c_int(-1), ctypes.c_int64(0)
+        check(self._lib.gbp_plan_resolve_host(terrain._h, self._h, tree._h, other._h, int(direction),
+                                              int(batch), int(bool(adaptive)), ctypes.byref(resume),
+                                              ctypes.byref(nres), _stream(device)), "plan_resolve")
+        return resume.value, nres.value
 
     def halves(self, terrain, ta, tb, first_half, n_halves, batch, seed, stream_a=101,
                stream_b=102, adaptive=False, first_stage=0, device=0):
@@ -602,6 +650,66 @@ class PlanWorkspace:
                                             int(n_halves), int(batch), int(seed), int(stream_a),
                                             int(stream_b), int(bool(adaptive)), int(first_stage),
                                             _stream(device)), "plan_halves")
+
+    def star_config(self, delta=3.0, max_pairs=1 << 18, max_shared=1 << 22, enable=True):
+        """gbp_plan_star_config: RRT*-Connect's insertion stages and its list of
+        kept connections (max_shared pairs)."""
+        check(self._lib.gbp_plan_star_config(self._h, int(bool(enable)), float(delta), int(max_pairs),
+                                             int(max_shared)), "star_config")
+
+    def shared_read(self, max_pairs=None, device=0):
+        """gbp_plan_shared_read_host: RRT*'s kept connections in list order and
+        the ranked best: (pairs [n][2] int32, best_a, best_b, best_cost)."""
+        n = ctypes.c_int64(0)
+        ba, bb, bc = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_double(np.inf)
+        if max_pairs is None:  # the length first, then the pairs
+            check(self._lib.gbp_plan_shared_read_host(self._h, 0, None, ctypes.byref(n), None, None,
+                                                      None, _stream(device)), "shared_read")
+            max_pairs = n.value
+        pairs = np.empty((int(max_pairs), 2), np.int32)
+        check(self._lib.gbp_plan_shared_read_host(self._h, pairs.shape[0], _np_ptr(pairs),
+                                                  ctypes.byref(n), ctypes.byref(ba), ctypes.byref(bb),
+                                                  ctypes.byref(bc), _stream(device)), "shared_read")
+        return pairs[:min(n.value, pairs.shape[0])], ba.value, bb.value, bc.value
+
+    def shared_load(self, ta, tb, pairs, device=0):
+        """gbp_plan_shared_load_host: replaces the kept connections by `pairs`
+        ([n][2], vertices of ta / tb), resets the best and ranks the list with
+        the trees' current g.  GbpError E_INVALID_ARG, nothing changed, when an
+        index is outside its tree or n exceeds max_shared."""
+        p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        check(self._lib.gbp_plan_shared_load_host(self._h, ta._h, tb._h, p.shape[0], _np_ptr(p),
+                                                  _stream(device)), "shared_load")
+
+    def shared_remap(self, ta, tb, remap_a=None, remap_b=None, n_a=None, n_b=None, device=0):
+        """gbp_plan_shared_remap_dev: the kept connections through a prune or a
+        re-root.  remap_a / remap_b: int32 device tensors as gbp_tree_prune_dev
+        / gbp_tree_reroot_dev write them (numpy arrays are uploaded), None =
+        that tree did not change (n_* then defaults to its size).  ta / tb are
+        the trees after the change.  Returns the stats dict (n_before, n_kept,
+        n_dropped_a, n_dropped_b, error), read back after the call."""
+        dev = torch.device("cuda", int(device))
+
+        def arg(r, n, tree):
+            if r is None:
+                return None, (len(tree) if n is None else int(n))
+            r = torch.as_tensor(np.ascontiguousarray(r, np.int32) if not isinstance(r, torch.Tensor)
+                                else r).to(dev).contiguous()
+            if r.dtype != torch.int32:
+                raise ValueError("a remap is int32")
+            return r, (r.numel() if n is None else int(n))
+
+        ra, na = arg(remap_a, n_a, ta)
+        rb, nb = arg(remap_b, n_b, tb)
+        st = torch.zeros(5, dtype=torch.int64, device=dev)
+        check(self._lib.gbp_plan_shared_remap_dev(self._h, ta._h, tb._h, _ptr(ra), na, _ptr(rb), nb,
+                                                  _ptr(st), _stream(device)), "shared_remap")
+        vals = st.cpu().tolist()
+        return dict(zip((name for name, _ in L.SharedStats._fields_), vals))
+
+    def tree_path(self, ta, tb, ia=-1, ib=-1, max_states=256, device=0):
+        """tree_path(ta, tb, ia, ib, ws=self): ia = ib = -1 takes the ranked best."""
+        return tree_path(ta, tb, ia, ib, ws=self, max_states=max_states, device=device)
 
     def nearest(self, tree, queries):
         """gbp_tree_nearest_dev: nearest vertex of `tree` per query (device tensors)."""
@@ -625,6 +733,30 @@ class PlanWorkspace:
                                              _np_ptr(res), _np_ptr(vtx), ctypes.byref(k)),
               "extend_tree_host")
         return res, vtx, k.value
+
+
+def tree_path(ta, tb, ia, ib, ws=None, max_states=256, device=0, grow=True):
+    """gbp_tree_path_host: the joined path of two device trees (ta's root ->
+    ia, then tb's ib -> root without ib) without reading the trees:
+    (states [n][8], actions [n - 1][10], info), info a dict of n_states,
+    n_from_a, n_from_b, error (PATH_E_*), length.  ia = ib = -1 with a
+    PlanWorkspace: RRT*'s ranked best (n_states = 0 when there is none).  A
+    path longer than max_states reports PATH_E_SHORT and the length needed;
+    with `grow` the call is repeated once with that length."""
+    lib = L.load()
+    while True:
+        s, a = np.empty((max(int(max_states), 0), 8)), np.empty((max(int(max_states), 0), 10))
+        pi = L.PathInfo()
+        check(lib.gbp_tree_path_host(ta._h, int(ia), tb._h, int(ib), ws._h if ws is not None else None,
+                                     s.shape[0], _np_ptr(s) if s.size else None,
+                                     _np_ptr(a) if a.size else None, ctypes.byref(pi),
+                                     _stream(device)), "tree_path")
+        info = {k: getattr(pi, k) for k, _ in L.PathInfo._fields_}
+        if grow and pi.error == L.PATH_E_SHORT and pi.n_states > s.shape[0]:
+            max_states, grow = pi.n_states, False
+            continue
+        n = 0 if pi.error else pi.n_states
+        return s[:n], a[:max(n - 1, 0)], info
 
 
 def nearest(queries, vertices):

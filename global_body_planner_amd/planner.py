@@ -234,11 +234,60 @@ def plan_rrt_connect_device(data, start, goal, **kw):
     return plan_rrt_connect(data, start, goal, algorithm=3, **kw)
 
 
-def plan_rrt_star_connect(data, start, goal, device_loop=False, **kw):
+def plan_rrt_star_connect(data, start, goal, device_loop=False, init_shared=None, **kw):
     """RRTStarConnectClass::buildRRTStarConnect, batch-synchronous (algorithm 1;
     algorithm 5 with device_loop: the search resident on the device, the
-    insertions' choose-parent / rewire replayed in HBM)."""
-    return plan_rrt_connect(data, start, goal, algorithm=5 if device_loop else 1, **kw)
+    insertions' choose-parent / rewire replayed in HBM).
+
+    init_shared ([n][2], with device_loop and init_trees): the warm start also
+    takes the earlier run's kept connections (pairs of a vertex of tree a and
+    one of tree b, in list order), so the continuation goes on with that list
+    and its best instead of starting a new ranking.  The flat C entry's
+    parameter record has no room for a list, so this form runs the same device
+    search through ReplanSession (the engine's own entries) and returns the
+    fields that search produces: found, halves, solutions (carried + new),
+    rewires, meet_a / meet_b and path_cost (the best pair and its cost),
+    vertices_a / vertices_b, a, b (the trees), shared (the final list), states,
+    actions, reported_length, reported_yaw, path_duration.  It takes batch,
+    seed, max_time, max_halves, init_trees, first_half, extend_base, adaptive
+    and device."""
+    if init_shared is None:
+        return plan_rrt_connect(data, start, goal, algorithm=5 if device_loop else 1, **kw)
+    if not device_loop or kw.get("init_trees") is None:
+        raise ValueError("init_shared continues a device search: device_loop=True and init_trees")
+    known = {"batch", "seed", "max_time", "max_halves", "init_trees", "first_half", "extend_base",
+             "adaptive", "device", "trees"}
+    if set(kw) - known:
+        raise ValueError(f"not taken with init_shared: {sorted(set(kw) - known)}")
+    from . import engine
+    own = not isinstance(data, engine.Terrain)
+    T = engine.Terrain.from_data(data, device=kw.get("device", 0)) if own else data
+    try:
+        s = ReplanSession(T, adaptive=kw.get("adaptive", False))
+        s.begin(start, goal, batch=kw.get("batch", 64), seed=kw.get("seed", 20251018),
+                init_trees=kw["init_trees"], first_half=kw.get("first_half", 0),
+                extend_base=kw.get("extend_base", 0), init_shared=init_shared)
+        h0 = s.half
+        found = s.search(kw.get("max_time", 5.0), kw.get("max_halves", 0))
+        st = s.status
+        pairs, best, cost = s.shared_connections()
+        path = s.best_path()
+        a, b = s.dump()
+        out = dict(found=int(found), halves=s.half - h0, solutions=len(pairs),
+                   rewires=st["stat_rewires"], meet_a=best[0], meet_b=best[1],
+                   path_cost=cost if found else 0.0, vertices_a=len(a["parent"]),
+                   vertices_b=len(b["parent"]), a=a, b=b, shared=pairs,
+                   ext_counter=st["ext_counter"],
+                   states=path["states"] if path else np.zeros((0, 8)),
+                   actions=path["actions"] if path else np.zeros((0, 10)),
+                   reported_length=path["length"] if path else 0.0,
+                   reported_yaw=path["yaw"] if path else 0.0,
+                   path_duration=path["duration"] if path else 0.0)
+        s.end()
+        return out
+    finally:
+        if own:
+            T.close()
 
 
 def plan_rrt_connect_anytime(data, start, goal, max_time_opt=1.0, device_loop=False, **kw):
@@ -386,3 +435,224 @@ def attempt_connect(terrain, s_existing, s, direction, t_s=None, adaptive=False,
     if rc != 0:
         raise _lib.GbpError(rc, "gbp_attempt_connect_batch")
     return res, sn, an
+
+
+# ---- the search kept on the device between plans ------------------------------------
+def _yaw_distance(q1, q2):
+    """planning_utils::stateYawDistance with glibc's atan2 (math.atan2)."""
+    import math
+    y1, y2 = math.atan2(q1[4], q1[3]), math.atan2(q2[4], q2[3])
+    lo, hi = min(y1, y2), max(y1, y2)
+    return min(hi - lo, lo + 2 * math.pi - hi)
+
+
+class ReplanSession:
+    """RRT*-Connect kept alive in HBM between plans: the Python form of the C++
+    `ReplanSession` (include/gbp_planner.h), written over the engine's own
+    entries (engine.PlanWorkspace / engine.DeviceTree), so it holds the same
+    trees, list of kept connections and best as the C++ class and as
+    plan_rrt_star_connect(device_loop=True) for the same arguments.
+
+    terrain: an engine.Terrain, which the caller updates in place
+    (Terrain.update) before map_changed.  The search is algorithm 5's: target
+    streams 401 / 402, groups of half-iterations with one status read each,
+    FRAGILE halts re-decided on the host and resumed."""
+
+    def __init__(self, terrain, adaptive=False):
+        self.T = terrain
+        self.adaptive = bool(adaptive)
+        self.ws = None
+
+    # -- life cycle ---------------------------------------------------------------
+    def begin(self, start, goal, batch=1024, delta=3.0, seed=20251018, init_trees=None,
+              first_half=0, extend_base=0, init_shared=None):
+        """Sets the search up as buildRRTStarConnectDevice does.  init_trees,
+        first_half, extend_base: a warm start as plan_rrt_connect takes it;
+        init_shared ([n][2]): the kept connections the continuation starts
+        with, loaded and ranked on the device (BatchStats::warm_shared)."""
+        from . import engine
+        self.end()
+        if first_half < 0 or first_half & 1 or extend_base < 0:
+            raise ValueError("a warm start of RRT*-Connect begins at an even half")
+        self.batch, self.delta, self.seed = int(batch), float(delta), int(seed)
+        self.ws = engine.PlanWorkspace(self.T, self.batch)
+        self.pairs_cap = max(1 << 18, 8 * self.batch)
+        self.ws.star_config(self.delta, self.pairs_cap, 1 << 22)
+        cap = max(1 << 16, 4 * self.batch)
+        roots = (start, goal)
+        self.trees = []
+        for k in range(2):
+            t = None if init_trees is None else init_trees[k]
+            n = 0 if t is None else len(t["parent"])
+            dt = engine.DeviceTree(roots[k] if n == 0 else np.asarray(t["v"])[0], device=self.T.device,
+                                   capacity=max(cap, 2 * n))
+            if n:
+                dt.load(t["v"], t["act"], t["parent"])
+            self.trees.append(dt)
+        self.known = [len(t) for t in self.trees]
+        warm = init_trees is not None or first_half > 0
+        self.ws.reset(self.T.device, extend_counter=extend_base if warm else 0)
+        if init_shared is not None and len(init_shared):
+            self.ws.shared_load(self.trees[0], self.trees[1], init_shared, device=self.T.device)
+        self.half = int(first_half)
+        self.group = 2
+        self.g_max = max(2, min(64, (1 << 21) // self.batch)) & ~1
+        self.status = self.ws.status(self.T.device)
+        self._remap = [None, None]
+        return self
+
+    def end(self):
+        self.ws = None
+        self.trees = None
+
+    @property
+    def active(self):
+        return self.ws is not None
+
+    def _need(self):
+        if self.ws is None:
+            raise _lib.GbpError(_lib.E_BAD_HANDLE, "ReplanSession: begin was not called")
+
+    # -- the search ---------------------------------------------------------------
+    def _run_group(self):
+        T, ws, (ta, tb) = self.T, self.ws, self.trees
+        for k, t in enumerate(self.trees):   # room for `group` halves of appends
+            c, need = t.capacity(), self.known[k] + self.group * self.batch
+            if need > c:
+                t.reserve(max(2 * c, need))
+        kw = dict(seed=self.seed, stream_a=401, stream_b=402, adaptive=self.adaptive, device=T.device)
+        ws.halves(T, ta, tb, self.half, self.group, self.batch, **kw)
+        st = ws.status(T.device)
+        while st["halt"]:
+            h0 = st["halt_half"]
+            k = h0 & 1
+            if st["halt"] & _lib.PLAN_HALT_STAR_PAIRS:   # a half's neighbour pairs outgrew the sets
+                self.pairs_cap = max(2 * self.pairs_cap, st["star_pairs"] + st["star_pairs"] // 4)
+                ws.star_config(self.delta, self.pairs_cap, 1 << 22)
+            resume, _ = ws.resolve(T, self.trees[k], self.trees[k ^ 1],
+                                   _lib.FORWARD if k == 0 else _lib.REVERSE, self.batch,
+                                   self.adaptive, T.device)
+            if resume < 0:
+                raise _lib.GbpError(_lib.E_INVALID_ARG, "plan resolve: nothing halted")
+            ws.halves(T, ta, tb, h0, self.half + self.group - h0, self.batch, first_stage=resume, **kw)
+            st = ws.status(T.device)
+        if st["error"]:
+            raise _lib.GbpError(_lib.E_SHAPE, f"device planner loop: status.error {st['error']}")
+        self.known = [len(t) for t in self.trees]
+        self.half += self.group
+        self.status = st
+
+    def search(self, max_time, max_halves=0):
+        """Pairs of half-iterations until max_time seconds or max_halves of this
+        call; halves and the extend counter go on from the last call.  Returns
+        whether a connection is held."""
+        import time
+        self._need()
+        t0, h0 = time.perf_counter(), self.half
+        while time.perf_counter() - t0 < max_time and (max_halves <= 0 or
+                                                      self.half - h0 + 2 <= max_halves):
+            if max_halves > 0:
+                self.group = min(self.group, (max_halves - (self.half - h0)) & ~1)
+            self._run_group()
+            self.group = min(self.group * 2, self.g_max)
+        return self.status["best_a"] >= 0
+
+    # -- the map changed, the robot moved ----------------------------------------------
+    def _remap_buf(self, k, n):
+        import torch
+        if self._remap[k] is None or self._remap[k].numel() < n:
+            self._remap[k] = torch.empty(max(n, 1 << 12), dtype=torch.int32,
+                                         device=self.T.torch_device)
+        return self._remap[k]
+
+    def _carry(self, ra, rb, before):
+        st = self.ws.shared_remap(self.trees[0], self.trees[1], ra, rb, before[0], before[1],
+                                  device=self.T.device)
+        self.status = self.ws.status(self.T.device)
+        if st["error"]:
+            raise _lib.GbpError(_lib.E_INVALID_ARG, "kept connections: an index outside its tree")
+        return st
+
+    def map_changed(self):
+        """The terrain was updated in place: both trees pruned where they are,
+        the list carried through the prunes' device remaps and ranked again.
+        Returns (prune stats of tree a and b, shared stats)."""
+        self._need()
+        before = list(self.known)
+        stats = []
+        for k, direction in enumerate((_lib.FORWARD, _lib.REVERSE)):
+            buf = self._remap_buf(k, before[k])
+            stats.append(self.trees[k].revalidate(self.T, direction, self.adaptive, remap_dev=buf)[1])
+            self.known[k] = stats[k]["n_kept"]
+        return tuple(stats), self._carry(self._remap[0], self._remap[1], before)
+
+    def robot_at(self, where, test_edges=False):
+        """The robot stands on start-tree vertex `where` (an int), or on a state
+        of the current best path ([8] values, matched bit for bit among the
+        path's start-tree states; the chain's vertex indices come from the
+        parents alone, 4 bytes per vertex of tree a).  Returns (re-root stats,
+        shared stats)."""
+        self._need()
+        if np.ndim(where) == 0:
+            vertex = int(where)
+        else:
+            path = self.best_path()
+            if path is None:
+                raise _lib.GbpError(_lib.E_INVALID_ARG, "ReplanSession: no path to locate the robot on")
+            parent = self.trees[0].read_parents()
+            chain = [self.status["best_a"]]
+            while chain[-1] != 0 and len(chain) <= len(parent):
+                chain.append(int(parent[chain[-1]]))
+            chain = chain[::-1]
+            s = np.ascontiguousarray(where, np.float64).reshape(8)
+            hit = [v for v, row in zip(chain, path["states"][:path["n_from_a"]])
+                   if row.tobytes() == s.tobytes()]
+            if not hit:
+                raise _lib.GbpError(_lib.E_INVALID_ARG,
+                                    "ReplanSession: the state is no start-tree vertex of the path")
+            vertex = hit[0]
+        before = list(self.known)
+        buf = self._remap_buf(0, before[0])
+        stats = self.trees[0].reroot(vertex, self.T if test_edges else None, _lib.FORWARD,
+                                     self.adaptive, remap_dev=buf)[1]
+        self.known[0] = stats["n_kept"]
+        return stats, self._carry(buf, None, before)
+
+    # -- what the search holds --------------------------------------------------------
+    def best_path(self):
+        """The joined path of the best kept connection, extracted on the device
+        (neither tree is read): a dict of states, actions, length, yaw, cost,
+        duration, n_from_a; None when no connection is held."""
+        self._need()
+        if self.status["best_a"] < 0 or self.status["best_b"] < 0:
+            return None
+        s, a, info = self.ws.tree_path(self.trees[0], self.trees[1], device=self.T.device)
+        if info["error"]:
+            raise _lib.GbpError(_lib.E_SHAPE, "ReplanSession: the trees' parents are no chains")
+        if info["n_states"] < 1:
+            return None
+        na, n = info["n_from_a"], info["n_states"]
+        s_ib = self.trees[1].read_state(self.status["best_b"])   # the goal chain's yaw sum ends there
+        ya = yb = 0.0
+        for i in range(1, na):
+            ya = ya + _yaw_distance(s[i - 1], s[i])
+        for i in range(n - 1, na, -1):
+            yb = yb + _yaw_distance(s[i], s[i - 1])
+        if n > na:
+            yb = yb + _yaw_distance(s[na], s_ib)
+        duration = 0.0
+        for row in a:
+            duration += row[6] + row[7]
+        return dict(states=s, actions=a, length=info["length"], yaw=ya + yb, cost=info["length"],
+                    duration=duration, n_from_a=na)
+
+    def dump(self):
+        """Both trees read back: (a, b) dicts of v, act, parent, g."""
+        self._need()
+        return tuple(dict(zip(("v", "act", "parent", "g"), t.read())) for t in self.trees)
+
+    def shared_connections(self):
+        """(pairs [n][2] in list order, (best_a, best_b), best_cost)."""
+        self._need()
+        pairs, ba, bb, bc = self.ws.shared_read(device=self.T.device)
+        return pairs, (ba, bb), bc

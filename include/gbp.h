@@ -580,6 +580,14 @@ int gbp_tree_prune_dev(gbp_tree *tree, int64_t n, const uint8_t *edge_valid, int
  * B.  Host remap[size of the tree before] (may be NULL) and stats[1]. */
 int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
                              int32_t *remap, gbp_prune_stats *stats, int64_t *n_resolved);
+/* The same, with stage B's remap also left in the caller's device array
+ * remap_dev[remap_cap] (its first n_before entries; GBP_E_SHAPE, nothing
+ * changed, when the tree holds more than remap_cap vertices), for a caller
+ * that carries indices of its own through the prune on the device
+ * (gbp_plan_shared_remap_dev).  remap_dev == NULL: gbp_tree_revalidate_host. */
+int gbp_tree_revalidate_keep_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
+                                  int32_t *remap, int32_t *remap_dev, int64_t remap_cap,
+                                  gbp_prune_stats *stats, int64_t *n_resolved);
 
 /* ---- a tree re-rooted at one of its vertices ----------------------------------
  * The robot executes its plan: at the next call it stands on a later state of
@@ -631,6 +639,11 @@ int gbp_tree_reroot_last(double ms[3], int64_t *launches);
  * new_root is outside the tree or the direction is bad; the tree is unchanged. */
 int gbp_tree_reroot_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, int direction,
                          int adaptive, int32_t *remap, gbp_reroot_stats *stats, int64_t *n_resolved);
+/* The same, with the remap also left in the caller's device array
+ * remap_dev[remap_cap], as gbp_tree_revalidate_keep_host leaves the prune's. */
+int gbp_tree_reroot_keep_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, int direction,
+                              int adaptive, int32_t *remap, int32_t *remap_dev, int64_t remap_cap,
+                              gbp_reroot_stats *stats, int64_t *n_resolved);
 
 /* ---- the device planner loop (RRTConnectClass::runRRTConnect,
  *      rrt_connect.cpp:230-314, batch-synchronous) ---------------------------
@@ -751,6 +764,83 @@ int gbp_plan_halves_dev(gbp_terrain *t, gbp_plan_ws *ws, gbp_tree *Ta, gbp_tree 
  * to RRT-Connect. */
 int gbp_plan_star_config(gbp_plan_ws *ws, int enable, double delta, int64_t max_pairs,
                          int64_t max_shared);
+/* ---- RRT*'s kept connections between searches -----------------
+ * The REACHED connections of a run are pairs (a, b), a vertex of Ta and one of
+ * Tb, listed in the order stage 5 appended them; status n_shared is the list's
+ * length and best_a / best_b / best_cost the cheapest of them.  A kept
+ * connection's two vertices need not hold the same state bit for bit (vertex
+ * b of a connection into Tb is the pair check's returned s_new, not a copy of
+ * a's row: DESIGN 5.10), so no entry compares the rows.  All three entries
+ * need RRT* configured (gbp_plan_star_config), else GBP_E_UNSUPPORTED, and
+ * order themselves behind the workspace's replay stream as well as `stream`;
+ * the planner call that follows must use the same `stream`.  The first call
+ * after gbp_plan_star_config set or raised max_shared allocates scratch of
+ * the list's size (when it replaces a smaller one it synchronises the device).
+ *
+ * gbp_plan_shared_read_host: pairs[min(*n, max)][2] in list order, *n = the
+ * list's length, the status's best; any output may be NULL.  Synchronous. */
+int gbp_plan_shared_read_host(gbp_plan_ws *ws, int64_t max, int32_t *pairs, int64_t *n,
+                              int32_t *best_a, int32_t *best_b, double *best_cost,
+                              gbp_stream stream);
+/* Replaces the list by the n host pairs[n][2], sets n_shared and the length
+ * the ranking reads, resets the best to none (best_cost = INFINITY, best_a =
+ * best_b = -1) and ranks the new list with the trees' current g
+ * (rrt_star_connect.cpp:181-193: NaN skipped, strictly cheaper, ties to the
+ * earliest).  The pairs are checked on the device in one pass before anything
+ * changes: GBP_E_INVALID_ARG, list and best as they were, when an index is
+ * outside [0, its tree's count) or n exceeds max_shared.  Synchronous. */
+int gbp_plan_shared_load_host(gbp_plan_ws *ws, gbp_tree *Ta, gbp_tree *Tb, int64_t n,
+                              const int32_t *pairs, gbp_stream stream);
+typedef struct {
+  int64_t n_before;     /* pairs listed before the call                          */
+  int64_t n_kept;       /* ... and after it                                      */
+  int64_t n_dropped_a;  /* dropped: its vertex of Ta is gone (whatever Tb's is)  */
+  int64_t n_dropped_b;  /* dropped: only its vertex of Tb is gone                */
+  int64_t error;        /* 1: a listed index outside [0, n_a) / [0, n_b): list,
+                           length and best are unchanged (n_kept etc. undefined) */
+} gbp_shared_stats;
+/* The list through a prune or a re-root of the trees.  remap_a[n_a] /
+ * remap_b[n_b] are the device arrays gbp_tree_prune_dev / gbp_tree_reroot_dev
+ * wrote for Ta / Tb (NULL: that tree did not change, n_* = its size); Ta and
+ * Tb are the trees after the change.  Pair (a, b) is kept when remap_a[a] >= 0
+ * and remap_b[b] >= 0 and becomes (remap_a[a], remap_b[b]); kept pairs keep
+ * their order.  Then, in the same sequence: n_shared and the ranking's length
+ * set, the best reset to none, the survivors ranked with the trees' current g,
+ * device stats[1] written (may be NULL).  Enqueue-only.  n_a / n_b out of step
+ * with the remaps' lengths or the trees is the caller's error. */
+int gbp_plan_shared_remap_dev(gbp_plan_ws *ws, gbp_tree *Ta, gbp_tree *Tb, const int32_t *remap_a,
+                              int64_t n_a, const int32_t *remap_b, int64_t n_b,
+                              gbp_shared_stats *stats, gbp_stream stream);
+
+/* ---- the joined path of two device trees (rrt_connect.cpp:386-401) ----------
+ * Ta's root -> vertex ia, then Tb's vertex ib -> root without ib itself, Tb's
+ * edges carrying the child's action: device states[n_states][8],
+ * actions[n_states - 1][10] (both 16-byte aligned), device info[1].  One
+ * workgroup: one lane walks each parent chain into the tree's level-queue
+ * scratch (so no other call on either tree may be in flight), bounded by the
+ * tree's count; then all lanes gather the rows.  ia = ib = -1 with a workspace
+ * (RRT* configured): the status's best_a / best_b, read on the device behind
+ * the workspace's replay stream; with no best connection n_states = 0 and
+ * length = INFINITY.  Yaw and duration are the host's, over the returned
+ * path.  Nothing is written past max_states rows. */
+#define GBP_PATH_E_CHAIN 1 /* ia / ib or a parent outside its tree, or no root within count steps */
+#define GBP_PATH_E_SHORT 2 /* max_states < n_states (the length needed); no row written */
+typedef struct {
+  int32_t n_states;   /* states of the path (0: error GBP_PATH_E_CHAIN, or no best connection) */
+  int32_t n_from_a;   /* of them Ta's (root .. ia)                                              */
+  int32_t n_from_b;   /* ... and Tb's (ib's parent .. root)                                     */
+  int32_t error;      /* 0 or GBP_PATH_E_*                                                      */
+  double length;      /* g_a[ia] + g_b[ib]                                                      */
+} gbp_path_info;
+int gbp_tree_path_dev(gbp_tree *Ta, int32_t ia, gbp_tree *Tb, int32_t ib, gbp_plan_ws *ws,
+                      int64_t max_states, double *states, double *actions, gbp_path_info *info,
+                      gbp_stream stream);
+/* the same with host outputs (states / actions hold max_states rows; the
+ * first n_states / n_states - 1 are written); synchronous */
+int gbp_tree_path_host(gbp_tree *Ta, int32_t ia, gbp_tree *Tb, int32_t ib, gbp_plan_ws *ws,
+                       int64_t max_states, double *states, double *actions, gbp_path_info *info,
+                       gbp_stream stream);
+
 /* diagnostics: per half-iteration timing events (hipEvents with timing, on
  * the streams the stages run on) while enabled; gbp_plan_stage_times adds up
  * every timed half completed so far, in microseconds:

@@ -490,6 +490,16 @@ struct BatchStats {
   const double *warm_a[2] = {nullptr, nullptr};
   const int32_t *warm_parent[2] = {nullptr, nullptr};
   int64_t warm_half = 0, warm_extend = 0;
+  // in (buildRRTStarConnectDevice's warm start): the kept connections the
+  // continuation starts with, warm_shared_n pairs (vertex of tree 0, vertex of
+  // tree 1) in list order, loaded and ranked on the device
+  // (gbp_plan_shared_load_host) once the warm trees are: the search then
+  // continues the earlier run's list and best instead of starting a new
+  // ranking.  Without it a warm start begins with no connection, as before.
+  const int32_t *warm_shared = nullptr;
+  int64_t warm_shared_n = 0;
+  // in (buildRRTStarConnectDevice): receives the final list of kept connections when set
+  std::vector<std::array<int32_t, 2>> *shared_dump = nullptr;
   // diagnostics (device loop): time each half-iteration's stage groups
   // (gbp_plan_stage_timing) into stage_us (half, stages 0-3, 6, 7, 4-5)
   bool stage_timing = false;
@@ -716,6 +726,89 @@ class RRTStarConnectClass : public RRTConnectClass {
   void insertStar(PlannerClass &T, FastTerrainMap &terrain, int dir, const std::vector<int> &added,
                   const std::vector<int> &nearest, const std::vector<Action> &a_new,
                   BatchStats *stats);
+};
+
+// ---- ReplanSession: RRT*-Connect kept alive on the device between plans ---------
+// What gbp_plan_shared_remap_dev did to the list of kept connections.
+struct SharedStats {
+  int64_t n_before = 0;     // connections listed before
+  int64_t n_kept = 0;       // ... and after
+  int64_t n_dropped_a = 0;  // dropped: its start-tree vertex is gone
+  int64_t n_dropped_b = 0;  // dropped: only its goal-tree vertex is gone
+};
+
+// The node's loop (terrainMapCallback, then callPlanner on every tick,
+// global_body_planner.cpp:37-131) against one search that stays in HBM: the
+// stream, the plan workspace, both trees and RRT*'s list of kept connections
+// outlive a call.  The search is buildRRTStarConnectDevice's (algorithm 5: the
+// one that keeps many connections and runs anytime); an RRT-Connect session
+// is not offered.  Planner settings (seed aside: begin takes it) are this
+// object's, set through RRTStarConnectClass's setters before begin.
+//   begin      sets the search up as buildRRTStarConnectDevice does.
+//   search     runs pairs of half-iterations until max_time or max_halves of
+//              this call; halves and the extend counter go on from the last
+//              call.  A session that has only called begin and search holds
+//              the trees, list and best of buildRRTStarConnectDevice with the
+//              same arguments.  Returns whether a connection is held.
+//   mapChanged the terrain handle was updated in place (updateData /
+//              updateDataFlat): both trees are pruned where they are and the
+//              list is carried through the prunes' device remaps and ranked
+//              again.  Neither the remaps nor the list come to the host; the
+//              prune's own read-back (the edges' decisions and flags, for
+//              the FRAGILE re-decision) stays.
+//   robotAt    the robot stands on a vertex of the start tree (or on a state
+//              of the current best path): the start tree is re-rooted there,
+//              with test_edges its edges tested on the map as well, and the
+//              list carried through that remap.  The State form costs more
+//              than the vertex form: it extracts the best path (bestPath),
+//              reads the start tree's parent array (4 bytes per vertex, no
+//              state, action or g) for the chain's vertex indices
+//              (startTreePath) and takes the first path state equal to s bit
+//              for bit, as findStateAmong does on a dumped tree.  A caller
+//              that tracks vertex indices should pass the vertex.
+//   search's BatchStats: halves and iterations are added per call; rewires,
+//              solutions, targets, extends, attempts_checked, connects,
+//              fragile_resolved, depth_capped, vertices_* and meet_* are set
+//              to the session's totals so far (the device status counts
+//              from begin), so a caller summing calls must not add them.
+//              costHistory() grows as in a build: the best cost once per
+//              group of halves when it improved, and after a carry that
+//              changed it.
+//   bestPath   the joined path of the best kept connection, extracted on the
+//              device (gbp_tree_path_host; one row of the goal tree is read
+//              for the yaw sum, neither tree); fills pathLength / pathYaw /
+//              pathCost as a build does.  False when no connection is held.
+// The synchronous tree entries run on the terrain's own stream: the session
+// synchronises its stream before them and they return synchronised.
+class ReplanSession : public RRTStarConnectClass {
+ public:
+  ReplanSession();
+  ~ReplanSession();
+  ReplanSession(const ReplanSession &) = delete;
+  ReplanSession &operator=(const ReplanSession &) = delete;
+  void begin(FastTerrainMap &terrain, State s_start, State s_goal, int batch, double delta = 3.0,
+             uint64_t seed = 20251018);
+  bool search(double max_time, int64_t max_halves = 0, BatchStats *stats = nullptr);
+  void mapChanged(FastTerrainMap &terrain, PruneStats stats[2], SharedStats *shared = nullptr);
+  void robotAt(int32_t vertex, RerootStats &stats, SharedStats *shared = nullptr,
+               bool test_edges = false);
+  void robotAt(const State &s, RerootStats &stats, SharedStats *shared = nullptr,
+               bool test_edges = false);
+  bool bestPath(std::vector<State> &state_sequence, std::vector<Action> &action_sequence);
+  void dump(TreeDump &trees);
+  // the kept connections in list order; best (optional): {best_a, best_b} or {-1, -1}
+  void sharedConnections(std::vector<std::array<int32_t, 2>> &pairs,
+                         std::array<int32_t, 2> *best = nullptr, double *best_cost = nullptr);
+  void end();
+  bool active() const { return impl_ != nullptr; }
+  int32_t nextHalf() const;        // the half-iteration the next search starts with
+  int64_t extendCounter() const;   // the candidate stream's next extend index
+
+ private:
+  struct Impl;
+  Impl *impl_ = nullptr;
+  Impl &impl() const;  // throws EngineError(GBP_E_BAD_HANDLE) before begin
+  void carryShared(bool remap_a, bool remap_b, const int64_t n_before[2], SharedStats *shared);
 };
 
 // ---- implementation of the grid_map adapter (fast_terrain_map.cpp:31-91) -------

@@ -18,6 +18,11 @@ using gbp_amd::PlannerClass;
 using gbp_amd::RRTClass;
 using gbp_amd::RRTConnectClass;
 using gbp_amd::RRTStarConnectClass;
+// not the reference's: the search kept on the device between plans
+using gbp_amd::ReplanSession;
+using gbp_amd::PruneStats;
+using gbp_amd::RerootStats;
+using gbp_amd::SharedStats;
 namespace planning_utils = gbp_amd::planning_utils;
 using namespace gbp_amd::planning_utils;  // the reference's headers do the same (planning_utils.h)
 
