@@ -39,7 +39,6 @@ using namespace gbp;
 namespace {
 
 constexpr uint64_t EXTEND_STREAM = GBP_EXTEND_STREAM;
-constexpr int WAVE = 64;
 
 // CM == 1: the coordinate vectors are staged in LDS (bracket fix-up and the
 // bilinear x1/x2/y1/y2 then never touch global memory); CM == 2 computes

@@ -1,9 +1,12 @@
 // gbp_internal.h — definitions shared by the engine's translation units
 // (gbp_engine.hip: terrain, lookups, pair checks, samplers, extend, NN;
 // gbp_plan.hip: device trees and the device-resident planner loop;
+// gbp_tree_maint.hip: a device tree pruned against a changed terrain or
+// re-rooted at one of its vertices;
 // gbp_terrain.hip: a handle's heights updated in place and its host mirror;
 // gbp_replan.hip: RRT*'s kept connections carried between searches and the
-// joined path of two device trees).
+// joined path of two device trees): the handles, the block sizes, the device
+// buffers' carve lists, and a tree's allocations and copies.
 // Not part of the C ABI.
 #pragma once
 
@@ -15,10 +18,14 @@
 
 #include "gbp.h"
 #include "gbp_device.h"
+#include "gbp_hrow.h"
 #include "host/gbp_host_check.h"
 #include "host/gbp_terrain_patch.h"
 
 constexpr uint64_t GBP_EXTEND_STREAM = 0x45585444ull;  // "EXTD": newConfig's candidate stream
+constexpr int WAVE = 64;
+constexpr int TB = 256;   // threads of the grid-stride kernels
+constexpr int CB = 1024;  // threads (items) per compaction tile
 
 struct gbp_terrain {
   gbp_host::Terrain host;           // host copy (the values the device holds) for the
@@ -216,7 +223,8 @@ int stage_buf(DevBuf &b, F carve) {
 
 // ============================================================================
 // the planner's handles (gbp_plan.hip creates, fills and frees them;
-// gbp_replan.hip reads the trees and the kept connections)
+// gbp_tree_maint.hip replaces a tree's arrays; gbp_replan.hip reads the trees
+// and the kept connections)
 // ============================================================================
 struct gbp_tree {
   int device = 0;
@@ -239,6 +247,84 @@ struct gbp_tree {
   void *rv = nullptr;
   size_t rv_bytes = 0;
 };
+
+inline bool tree_ok(const gbp_tree *t) { return t && t->v && t->count; }
+
+__device__ __forceinline__ void copy8(double *d, const double *s) {
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = s[k];
+}
+
+// The tree's capacity-sized allocations, stated once, in allocation order;
+// tree_alloc, gbp_tree_reserve's copies and frees and gbp_tree_destroy all go
+// through this list (count and hm are gbp_tree_create's and
+// gbp_tree_destroy's own).  An allocation holds `parts` sub-arrays of
+// [capacity] rows back to back, so a sub-array's offset depends on the
+// capacity; a reserve carries the first `copied` of them over, the rest is
+// scratch.
+struct TreeArray {
+  size_t row;         // bytes per vertex of one sub-array
+  int parts = 1;
+  int copied = 1;
+  int64_t round = 1;  // rows allocated: the capacity rounded up to a multiple
+  size_t bytes(int64_t cap) const { return row * parts * (size_t)((cap + round - 1) / round * round); }
+  size_t part_offset(int k, int64_t cap) const { return row * k * (size_t)cap; }
+};
+template <class F>
+inline void for_each_tree_array(F f) {
+  f(&gbp_tree::v, TreeArray{64});
+  f(&gbp_tree::a, TreeArray{80});
+  f(&gbp_tree::g, TreeArray{8});
+  f(&gbp_tree::parent, TreeArray{4});
+  // child | sibling | prev | bfs[2]: the successor lists survive a reserve,
+  // the subtree update's two level queues are scratch
+  f(&gbp_tree::child, TreeArray{4, 5, 3});
+  // the fp16 rows in whole 64-row units (nh_sweep loads a unit's rows past the
+  // tree's end and masks their scores)
+  f(&gbp_tree::vh, TreeArray{2 * NH_ROW, 1, 1, 64});
+}
+
+inline void tree_free_arrays(gbp_tree *t) {
+  for_each_tree_array([&](auto m, const TreeArray &) {
+    if (t->*m) (void)hipFree(t->*m);
+    t->*m = nullptr;
+  });
+}
+
+// fresh arrays of `cap` rows in *t (what it held before is the caller's to
+// free); on failure nothing is allocated and *t is unchanged
+inline int tree_alloc(gbp_tree *t, int64_t cap) {
+  gbp_tree n = *t;
+  for_each_tree_array([&](auto m, const TreeArray &) { n.*m = nullptr; });
+  bool ok = true;
+  for_each_tree_array([&](auto m, const TreeArray &A) {
+    if (ok && hipMalloc(&(n.*m), A.bytes(cap)) != hipSuccess) {
+      n.*m = nullptr;
+      ok = false;
+    }
+  });
+  if (!ok) {
+    tree_free_arrays(&n);
+    return GBP_E_ALLOC;
+  }
+  n.sibling = n.child + cap;
+  n.prev = n.child + 2 * cap;
+  n.bfs = n.child + 3 * cap;
+  n.cap = cap;
+  *t = n;
+  return GBP_OK;
+}
+
+template <class T>
+inline int d2h(T *dst, const T *src, size_t count, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, s));
+  return GBP_OK;
+}
+template <class T>
+inline int h2d(T *dst, const T *src, size_t count, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, s));
+  return GBP_OK;
+}
 
 // the segment scans k_nn_hreduce lists (a fourth unit of a segment within
 // the threshold: the segment's rows in fp64) and their merge; one set for the

@@ -47,18 +47,9 @@
 // with decoupled look-back", 2016), so vertices land in exactly the order of
 // the host planner's insertion loop.
 //
-// A tree against a changed terrain (gbp_tree_revalidate_dev, gbp_tree_prune_dev):
-// k_prune_gather writes every edge as an attempt row for the validate kernels,
-// k_prune_seed / k_prune_jump find the vertices whose edges up to the root all
-// hold, k_prune_count / k_prune_scan / k_prune_rank number them in order and
-// k_prune_move_rows / k_prune_move_links move them into fresh arrays.
-//
-// A tree re-rooted at one of its vertices (gbp_tree_reroot_dev): the same
-// jumping with the new root as a second terminal and the depth below it summed
-// along (k_reroot_seed / k_reroot_jump), the compaction with the new root
-// placed first (k_reroot_count / k_reroot_scan / k_reroot_rank), the prune's
-// move, then g derived again level by level (k_reroot_levels / k_reroot_order
-// sort the vertices by depth, k_reroot_g_wide / k_reroot_g_narrow write g).
+// A tree pruned against a changed terrain or re-rooted at one of its vertices:
+// gbp_tree_maint.hip.  The fp16 rows' writer both share with the searches here:
+// gbp_hrow.h; a tree's allocations: gbp_internal.h.
 //
 // FRAGILE decisions (gbp.h) stop the sequence at the next gate: the kernel
 // that meets one sets status.halt; every later kernel of the group returns at
@@ -92,13 +83,12 @@ static_assert(sizeof(gbp_plan_status) == 216, "engine.PlanStatus mirrors this la
 // ============================================================================
 // handles
 // ============================================================================
-// gbp_tree, NsBuf, gbp_plan_la and gbp_plan_ws: gbp_internal.h (gbp_replan.hip shares them)
+// gbp_tree, NsBuf, gbp_plan_la and gbp_plan_ws, a tree's allocations and the
+// block sizes WAVE / TB / CB: gbp_internal.h (gbp_tree_maint.hip and
+// gbp_replan.hip share them)
 
 namespace {
 
-constexpr int WAVE = 64;
-constexpr int TB = 256;            // threads of the grid-stride kernels
-constexpr int CB = 1024;           // threads (items) per look-back tile
 constexpr int NN_MAX_CHUNKS = 32;  // partial slots per query at the largest batch
 constexpr uint32_t LOOKBACK_SPIN_LIMIT = 1u << 24;
 
@@ -116,10 +106,6 @@ __device__ __forceinline__ void raise_gate(gbp_plan_status *st, uint64_t seq) {
   atomicMin((unsigned long long *)&st->gate_seq, (unsigned long long)seq);
 }
 
-__device__ __forceinline__ void copy8(double *d, const double *s) {
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = s[k];
-}
 __device__ __forceinline__ void copy10(double *d, const double *s) {
 #pragma unroll
   for (int k = 0; k < 10; k++) d[k] = s[k];
@@ -253,11 +239,9 @@ __device__ __forceinline__ void ns_min(double &d, int &i, double od, int oi) {
 //     segment is scanned).
 // Rows with |F_k| >= 2^13 (|v_k| >= 128) or NaN mark the tree (hbad): its
 // searches scan in fp64.  So do queries with |G_k| >= 2^13 or NaN.
-constexpr int NH_ROW = 32;             // fp16 per row: F_hi[8] F_lo[8] F_hi[8] N_1 N_2 N_3 0[5]
-constexpr double NH_SCALE = 64.0;      // F = 64 v (exact)
-constexpr double NH_LIM = 8192.0;      // |F_k| < 2^13: |F|^2 * 2^-14 < 2^15 fits fp16
-constexpr double NH_NSCALE = 0x1p-14;  // the norm parts are |F|^2 * 2^-14 ...
-constexpr float NH_NCONST = 16384.0f;  // ... times 2^14 on the query side
+// The row's layout and its writer (NH_ROW, NH_SCALE, NH_LIM, NH_NSCALE, nh8,
+// nh_split, nn_put_hrow): gbp_hrow.h.
+constexpr float NH_NCONST = 16384.0f;  // the norm parts (|F|^2 * 2^-14) times 2^14 on the query side
 constexpr int NS_MAXQ = 32;            // k_nn_small: queries it takes (the connects')
 constexpr int NS_GQ = 4;               // ... scored together per pass
 constexpr int NS_TB = 256;
@@ -269,55 +253,7 @@ constexpr int NH_TB = 256;             // 4 independent waves per workgroup
 constexpr int NH_RTB = 256;            // reduce: workgroup size
 constexpr int NH_G = 16;               // reduce: lanes per query
 
-typedef _Float16 nh8 __attribute__((ext_vector_type(8)));
 typedef float nhacc __attribute__((ext_vector_type(16)));
-
-// fp16 hi + lo of a scaled coordinate (|x| < 2^13)
-__device__ __forceinline__ void nh_split(double x, _Float16 &hi, _Float16 &lo) {
-  hi = (_Float16)(float)x;
-  lo = (_Float16)(float)(x - (double)hi);
-}
-
-// row j of the fp16 rows; hm = {hmax[8], hbad}
-__device__ __forceinline__ void nn_put_hrow(_Float16 *__restrict__ vh, float *__restrict__ hm,
-                                            int64_t j, const double *s, bool init) {
-  nh8 fh, fl, nr;
-  double n = 0.0;
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    const double x = s[k] * NH_SCALE;
-    const bool ok = fabs(x) < NH_LIM;
-    bad = bad || !ok;
-    _Float16 hi, lo;
-    nh_split(ok ? x : 0.0, hi, lo);
-    fh[k] = hi;
-    fl[k] = lo;
-    n = n + x * x;
-    const float ax = ok ? (float)fabs(x) : 0.f;
-    if (!hm) continue;  // a query row
-    if (init)
-      hm[k] = ax;
-    else
-      atomicMax((unsigned int *)(hm + k), __float_as_uint(ax));
-  }
-  const double ns = bad ? 0.0 : n * NH_NSCALE;
-  const _Float16 n1 = (_Float16)(float)ns;
-  const double r1 = ns - (double)n1;
-  const _Float16 n2 = (_Float16)(float)r1;
-  const _Float16 n3 = (_Float16)(float)(r1 - (double)n2);
-  nr = nh8{n1, n2, n3, 0, 0, 0, 0, 0};
-  nh8 *r = (nh8 *)(vh + (int64_t)NH_ROW * j);
-  r[0] = fh;
-  r[1] = fl;
-  r[2] = fh;
-  r[3] = nr;
-  if (!hm) return;
-  if (init)
-    ((uint32_t *)hm)[8] = bad ? 1u : 0u;
-  else if (bad)
-    atomicOr((uint32_t *)hm + 8, 1u);
-}
 
 // items: query groups (NH_NT tiles) x segments of cps chunks (32 rows); at
 // most NN_MAX_CHUNKS * bmax partial slots (pm[seg * nq + qi])
@@ -2449,444 +2385,6 @@ __global__ void k_tree_load(gbp_tree t, int64_t n, const double *__restrict__ s,
   *t.count = (int32_t)n;
 }
 
-// ============================================================================
-// pruning a tree against a changed terrain (gbp_tree_revalidate_dev,
-// gbp_tree_prune_dev)
-// ============================================================================
-// Stage A: edge (parent[i] -> i), i in [1, n), as attempt row i - 1 of the
-// validate kernels: s = v[parent[i]], a = a[i].  One 16-B piece per thread, a
-// row's 9 pieces (4 of s, 5 of a) on consecutive lanes.  n must be the tree's
-// device count: otherwise nothing of the tree is read (every row zero) and
-// edge_valid[0] = 0 tells the caller.
-constexpr int PRUNE_PIECES = 9;
-__global__ __launch_bounds__(TB) void k_prune_gather(gbp_tree t, int32_t n, double2 *__restrict__ rs,
-                                                     double2 *__restrict__ ra,
-                                                     uint8_t *__restrict__ edge_valid,
-                                                     uint32_t *__restrict__ flags) {
-  const bool ok = *t.count == n;
-  const double2 *tv = (const double2 *)t.v, *ta = (const double2 *)t.a;
-  const int64_t pieces = (int64_t)(n - 1) * PRUNE_PIECES;
-  const int64_t first = (int64_t)blockIdx.x * TB + threadIdx.x;
-  for (int64_t x = first; x < pieces; x += (int64_t)gridDim.x * TB) {
-    const int64_t row = x / PRUNE_PIECES, i = row + 1;
-    const int k = (int)(x - row * PRUNE_PIECES);
-    double2 val = make_double2(0.0, 0.0);
-    if (k < 4) {
-      const int32_t p = ok ? t.parent[i] : -1;
-      if (p >= 0 && p < n) val = tv[4 * (int64_t)p + k];
-      rs[4 * row + k] = val;
-    } else {
-      if (ok) val = ta[5 * i + (k - 4)];
-      ra[5 * row + (k - 4)] = val;
-    }
-  }
-  if (first == 0) {  // the root is never tested
-    edge_valid[0] = ok ? 1 : 0;
-    flags[0] = 0;
-  }
-}
-
-// Stage B, the keep rule by pointer jumping.  A vertex's word is
-// (ancestor << 1) | dead: after r rounds its 2^r-th ancestor (the root once
-// the path is shorter) and whether one of the 2^r edges up to it failed.  A
-// round reads one buffer and writes the other, so every word read is the
-// previous round's whatever the workgroups' order; ceil(log2 n) rounds reach
-// the root from every vertex (a path has at most n - 1 edges).  A parent
-// outside [0, n) counts as a failed edge below the root.
-__global__ __launch_bounds__(TB) void k_prune_seed(const int32_t *__restrict__ parent,
-                                                   const uint8_t *__restrict__ edge_valid, int32_t n,
-                                                   uint32_t *__restrict__ w) {
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
-    uint32_t x = 0;  // the root: its own ancestor, never dead
-    if (i > 0) {
-      const int32_t p = parent[i];
-      x = (p < 0 || p >= n) ? 1u : ((uint32_t)p << 1) | (edge_valid[i] ? 0u : 1u);
-    }
-    w[i] = x;
-  }
-}
-
-__global__ __launch_bounds__(TB) void k_prune_jump(const uint32_t *__restrict__ src,
-                                                   uint32_t *__restrict__ dst, int32_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
-    const uint32_t x = src[i], y = src[x >> 1];
-    dst[i] = (y & ~1u) | ((x | y) & 1u);
-  }
-}
-
-// The order-preserving compaction without a wait between workgroups: tile b
-// (CB vertices) counts its kept vertices and its failed edges, one workgroup
-// scans the tiles' counts, then every tile ranks its vertices again from its
-// offset (the same ballots).
-__global__ __launch_bounds__(CB) void k_prune_count(const uint32_t *__restrict__ w,
-                                                    const uint8_t *__restrict__ edge_valid, int32_t n,
-                                                    uint2 *__restrict__ tile) {
-  __shared__ uint32_t sk[CB / WAVE], sb[CB / WAVE];
-  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
-  const bool in = i < n;
-  const bool keep = in && !(w[i] & 1u), bad = in && i > 0 && !edge_valid[i];
-  const unsigned long long mk = __ballot(keep), mb = __ballot(bad);
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
-    sk[threadIdx.x / WAVE] = (uint32_t)__popcll(mk);
-    sb[threadIdx.x / WAVE] = (uint32_t)__popcll(mb);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t k = 0, b = 0;
-    for (int q = 0; q < CB / WAVE; q++) {
-      k += sk[q];
-      b += sb[q];
-    }
-    tile[blockIdx.x] = make_uint2(k, b);
-  }
-}
-
-// one workgroup: toff[b] = the kept vertices of the tiles before b; the stats
-// record and the tree's new count
-__global__ __launch_bounds__(CB) void k_prune_scan(const uint2 *__restrict__ tile, int64_t ntile,
-                                                   uint32_t *__restrict__ toff, int32_t n,
-                                                   gbp_prune_stats *__restrict__ stats,
-                                                   int32_t *__restrict__ count) {
-  __shared__ uint32_t ws[CB / WAVE], wb[CB / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  uint32_t run = 0, bad = 0;  // the same in every thread
-  for (int64_t base = 0; base < ntile; base += CB) {
-    const int64_t b = base + threadIdx.x;
-    const uint2 c = b < ntile ? tile[b] : make_uint2(0u, 0u);
-    uint32_t incl = c.x, bsum = c.y;  // inclusive scan / sum over the wave
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, WAVE);
-      if (lane >= d) incl += up;
-      bsum += __shfl_xor(bsum, d, WAVE);
-    }
-    if (lane == WAVE - 1) ws[wv] = incl;
-    if (lane == 0) wb[wv] = bsum;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (int q = 0; q < CB / WAVE; q++) {
-      if (q < wv) woff += ws[q];
-      tot += ws[q];
-      bad += wb[q];
-    }
-    if (b < ntile) toff[b] = run + woff + incl - c.x;
-    run += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    stats->n_before = n;
-    stats->n_kept = run;
-    stats->n_edge_invalid = bad;
-    stats->n_inherited = (int64_t)n - run - bad;
-    *count = (int32_t)run;
-  }
-}
-
-__global__ __launch_bounds__(CB) void k_prune_rank(const uint32_t *__restrict__ w, int32_t n,
-                                                   const uint32_t *__restrict__ toff,
-                                                   int32_t *__restrict__ remap) {
-  __shared__ uint32_t sk[CB / WAVE];
-  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const bool keep = i < n && !(w[i] & 1u);
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) sk[wv] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t off = toff[blockIdx.x];
-  for (int q = 0; q < wv; q++) off += sk[q];
-  if (i < n) remap[i] = keep ? (int32_t)(off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))) : -1;
-}
-
-// the kept rows of v and a into the fresh arrays, in 16-B pieces like the gather
-__global__ __launch_bounds__(TB) void k_prune_move_rows(gbp_tree o, gbp_tree f, int32_t n,
-                                                        const int32_t *__restrict__ remap) {
-  const double2 *ov = (const double2 *)o.v, *oa = (const double2 *)o.a;
-  double2 *fv = (double2 *)f.v, *fa = (double2 *)f.a;
-  const int64_t pieces = (int64_t)n * PRUNE_PIECES;
-  for (int64_t x = (int64_t)blockIdx.x * TB + threadIdx.x; x < pieces; x += (int64_t)gridDim.x * TB) {
-    const int64_t i = x / PRUNE_PIECES;
-    const int k = (int)(x - i * PRUNE_PIECES);
-    const int64_t j = remap[i];
-    if (j < 0) continue;
-    if (k < 4)
-      fv[4 * j + k] = ov[4 * i + k];
-    else
-      fa[5 * j + (k - 4)] = oa[5 * i + (k - 4)];
-  }
-}
-
-// the next kept vertex of a successor list from c on (c itself included),
-// renumbered; -1 at the list's end.  A list holds at most n vertices: the walk
-// stops there whatever the arrays hold.
-__device__ __forceinline__ int32_t prune_next_kept(int32_t c, const int32_t *__restrict__ link,
-                                                   const int32_t *__restrict__ remap, int32_t n) {
-  for (int32_t steps = 0; c >= 0 && c < n && steps < n; c = link[c], steps++)
-    if (remap[c] >= 0) return remap[c];
-  return -1;
-}
-
-// a kept vertex's g (copied: it is g[parent] + poseDistance already), its
-// parent renumbered, its fp16 row (hm zeroed before this launch), and its
-// places in the successor lists: the old lists with the pruned vertices left
-// out, so each list keeps its order.  Every word written belongs to the
-// vertex's own fresh row.
-__global__ __launch_bounds__(TB) void k_prune_move_links(gbp_tree o, gbp_tree f, int32_t n,
-                                                         const int32_t *__restrict__ remap) {
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
-    const int32_t j = remap[i];
-    if (j < 0) continue;
-    const int32_t p = o.parent[i];
-    f.parent[j] = (p >= 0 && p < n) ? remap[p] : -1;
-    f.g[j] = o.g[i];
-    double s[8];
-    copy8(s, o.v + 8 * i);
-    nn_put_hrow(f.vh, f.hm, j, s, false);
-    f.child[j] = prune_next_kept(o.child[i], o.sibling, remap, n);
-    f.sibling[j] = prune_next_kept(o.sibling[i], o.sibling, remap, n);
-    f.prev[j] = prune_next_kept(o.prev[i], o.prev, remap, n);
-  }
-}
-
-// ============================================================================
-// re-rooting a tree at one of its vertices (gbp_tree_reroot_dev)
-// ============================================================================
-// The keep rule is the prune's word scheme with two terminals: the new root k
-// is its own ancestor and never dead, the old root is its own ancestor and
-// dead.  After the rounds a vertex's ancestor is k exactly when it lies below
-// k, and its dead bit then tells whether an edge between the two failed.  A
-// second pair of buffers carries the number of edges jumped so far (terminals
-// add 0): integer sums are associative, so the depth below k is exact.
-// edge_valid may be null (every edge holds); edge_valid[k] is never read.
-__global__ __launch_bounds__(TB) void k_reroot_seed(const int32_t *__restrict__ parent,
-                                                    const uint8_t *__restrict__ edge_valid, int32_t n,
-                                                    int32_t k, uint32_t *__restrict__ w,
-                                                    uint32_t *__restrict__ d) {
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
-    uint32_t x, e = 0;
-    if (i == k) {
-      x = (uint32_t)k << 1;
-    } else if (i == 0) {
-      x = 1u;
-    } else {
-      const int32_t p = parent[i];
-      const bool in = p >= 0 && p < n;
-      x = in ? ((uint32_t)p << 1) | ((edge_valid && !edge_valid[i]) ? 1u : 0u) : 1u;
-      e = in ? 1u : 0u;
-    }
-    w[i] = x;
-    d[i] = e;
-  }
-}
-
-__global__ __launch_bounds__(TB) void k_reroot_jump(const uint32_t *__restrict__ ws,
-                                                    const uint32_t *__restrict__ ds,
-                                                    uint32_t *__restrict__ wd,
-                                                    uint32_t *__restrict__ dd, int32_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
-    const uint32_t x = ws[i], y = ws[x >> 1];
-    wd[i] = (y & ~1u) | ((x | y) & 1u);
-    dd[i] = ds[i] + ds[x >> 1];
-  }
-}
-
-// kept: below k with no failed edge in between (a vertex on a cycle of a
-// malformed parent array reaches neither terminal and is outside)
-__device__ __forceinline__ bool reroot_below(uint32_t w, int32_t k) { return (w >> 1) == (uint32_t)k; }
-__device__ __forceinline__ bool reroot_kept(uint32_t w, int32_t k) {
-  return reroot_below(w, k) && !(w & 1u);
-}
-
-// The prune's compaction with k taken out of the order: a tile counts its
-// kept vertices other than k, those below k whose own edge failed, those not
-// below k, and the largest depth of a kept vertex.
-__global__ __launch_bounds__(CB) void k_reroot_count(const uint32_t *__restrict__ w,
-                                                     const uint32_t *__restrict__ d,
-                                                     const uint8_t *__restrict__ edge_valid, int32_t n,
-                                                     int32_t k, uint4 *__restrict__ tile) {
-  __shared__ uint32_t sk[CB / WAVE], sb[CB / WAVE], so[CB / WAVE], sd[CB / WAVE];
-  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
-  const bool in = i < n;
-  const uint32_t x = in ? w[i] : 1u;
-  const bool below = in && reroot_below(x, k);
-  const bool keep = below && !(x & 1u);
-  const bool bad = below && i != k && edge_valid && !edge_valid[i];
-  const unsigned long long mk = __ballot(keep && i != k), mb = __ballot(bad), mo = __ballot(in && !below);
-  uint32_t dep = keep ? d[i] : 0u;
-#pragma unroll
-  for (int s = 1; s < WAVE; s <<= 1) dep = max(dep, (uint32_t)__shfl_xor(dep, s, WAVE));
-  if ((threadIdx.x & (WAVE - 1)) == 0) {
-    sk[threadIdx.x / WAVE] = (uint32_t)__popcll(mk);
-    sb[threadIdx.x / WAVE] = (uint32_t)__popcll(mb);
-    so[threadIdx.x / WAVE] = (uint32_t)__popcll(mo);
-    sd[threadIdx.x / WAVE] = dep;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint4 t = make_uint4(0u, 0u, 0u, 0u);
-    for (int q = 0; q < CB / WAVE; q++) {
-      t.x += sk[q];
-      t.y += sb[q];
-      t.z += so[q];
-      t.w = max(t.w, sd[q]);
-    }
-    tile[blockIdx.x] = t;
-  }
-}
-
-// one workgroup: toff[b] = 1 + the kept vertices other than k of the tiles
-// before b (k itself is vertex 0); the stats record and the tree's new count
-__global__ __launch_bounds__(CB) void k_reroot_scan(const uint4 *__restrict__ tile, int64_t ntile,
-                                                    uint32_t *__restrict__ toff, int32_t n,
-                                                    gbp_reroot_stats *__restrict__ stats,
-                                                    int32_t *__restrict__ count) {
-  __shared__ uint32_t ws[CB / WAVE], wb[CB / WAVE], wo[CB / WAVE], wd[CB / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  uint32_t run = 1, bad = 0, out = 0, deep = 0;  // the same in every thread
-  for (int64_t base = 0; base < ntile; base += CB) {
-    const int64_t b = base + threadIdx.x;
-    const uint4 c = b < ntile ? tile[b] : make_uint4(0u, 0u, 0u, 0u);
-    uint32_t incl = c.x, bsum = c.y, osum = c.z, dmax = c.w;
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-      const uint32_t up = __shfl_up(incl, s, WAVE);
-      if (lane >= s) incl += up;
-      bsum += __shfl_xor(bsum, s, WAVE);
-      osum += __shfl_xor(osum, s, WAVE);
-      dmax = max(dmax, (uint32_t)__shfl_xor(dmax, s, WAVE));
-    }
-    if (lane == WAVE - 1) ws[wv] = incl;
-    if (lane == 0) {
-      wb[wv] = bsum;
-      wo[wv] = osum;
-      wd[wv] = dmax;
-    }
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (int q = 0; q < CB / WAVE; q++) {
-      if (q < wv) woff += ws[q];
-      tot += ws[q];
-      bad += wb[q];
-      out += wo[q];
-      deep = max(deep, wd[q]);
-    }
-    if (b < ntile) toff[b] = run + woff + incl - c.x;
-    run += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    stats->n_before = n;
-    stats->n_kept = run;
-    stats->n_outside = out;
-    stats->n_edge_invalid = bad;
-    stats->n_inherited = (int64_t)n - run - bad - out;
-    stats->depth = deep;
-    *count = (int32_t)run;
-  }
-}
-
-// remap (k -> 0, the other kept vertices from 1 in their order), every kept
-// vertex's depth under its new index, and the levels' sizes (hist zeroed
-// before this launch; an integer count does not depend on the atomics' order)
-__global__ __launch_bounds__(CB) void k_reroot_rank(const uint32_t *__restrict__ w,
-                                                    const uint32_t *__restrict__ d, int32_t n, int32_t k,
-                                                    const uint32_t *__restrict__ toff,
-                                                    int32_t *__restrict__ remap,
-                                                    uint32_t *__restrict__ depth,
-                                                    uint32_t *__restrict__ hist) {
-  __shared__ uint32_t sk[CB / WAVE];
-  const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const bool keep = i < n && reroot_kept(w[i], k);
-  const unsigned long long m = __ballot(keep && i != k);
-  if (lane == 0) sk[wv] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t off = toff[blockIdx.x];
-  for (int q = 0; q < wv; q++) off += sk[q];
-  if (i >= n) return;
-  const int32_t j = !keep ? -1 : i == k ? 0 : (int32_t)(off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)));
-  remap[i] = j;
-  if (j >= 0) {
-    depth[j] = d[i];
-    atomicAdd(&hist[d[i]], 1u);
-  }
-}
-
-// one workgroup, after the move: first[r] = the kept vertices of the levels
-// before r, r in [0, depth + 1] (hist keeps the sizes for k_reroot_order), and
-// the new root's action zeroed as k_tree_init writes it
-__global__ __launch_bounds__(CB) void k_reroot_levels(const uint32_t *__restrict__ hist,
-                                                      const gbp_reroot_stats *__restrict__ stats,
-                                                      uint32_t *__restrict__ first, double *__restrict__ a) {
-  __shared__ uint32_t ws[CB / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
-  const int64_t nl = stats->depth + 1;
-  uint32_t run = 0;
-  for (int64_t base = 0; base < nl; base += CB) {
-    const int64_t r = base + threadIdx.x;
-    const uint32_t c = r < nl ? hist[r] : 0u;
-    uint32_t incl = c;
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-      const uint32_t up = __shfl_up(incl, s, WAVE);
-      if (lane >= s) incl += up;
-    }
-    if (lane == WAVE - 1) ws[wv] = incl;
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (int q = 0; q < CB / WAVE; q++) {
-      if (q < wv) woff += ws[q];
-      tot += ws[q];
-    }
-    if (r < nl) first[r] = run + woff + incl - c;
-    run += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) first[nl] = run;
-  if (threadIdx.x < 10) a[threadIdx.x] = 0.0;
-}
-
-// the counting sort's scatter: order[first[r] ..] = the vertices of level r.
-// Their order within a level depends on the atomics and is immaterial: a
-// vertex's g depends on its parent's alone.
-__global__ __launch_bounds__(TB) void k_reroot_order(const uint32_t *__restrict__ depth,
-                                                     const int32_t *__restrict__ count,
-                                                     const uint32_t *__restrict__ first,
-                                                     uint32_t *__restrict__ hist,
-                                                     int32_t *__restrict__ order) {
-  const int64_t m = *count;
-  for (int64_t j = (int64_t)blockIdx.x * TB + threadIdx.x; j < m; j += (int64_t)gridDim.x * TB) {
-    const uint32_t r = depth[j];
-    order[first[r] + atomicSub(&hist[r], 1u) - 1u] = (int32_t)j;
-  }
-}
-
-// g of one vertex from its parent's, as k_tree_load derives it
-__device__ __forceinline__ void reroot_g(const gbp_tree &t, int32_t c) {
-  const int32_t p = t.parent[c];
-  t.g[c] = p >= 0 ? t.g[p] + pose_distance(t.v + 8 * (int64_t)p, t.v + 8 * (int64_t)c) : 0.0;
-}
-
-// g by levels.  A level's vertices read the g their parents' level wrote: the
-// two are separated by a kernel boundary (a level wider than a workgroup is a
-// launch of its own over its slice of `order`) or by the barrier between the
-// steps of the one workgroup that walks a run of narrow levels.  No workgroup
-// waits for another.
-__global__ __launch_bounds__(TB) void k_reroot_g_wide(gbp_tree t, const int32_t *__restrict__ order,
-                                                      int64_t lo, int64_t hi) {
-  for (int64_t x = lo + (int64_t)blockIdx.x * TB + threadIdx.x; x < hi; x += (int64_t)gridDim.x * TB)
-    reroot_g(t, order[x]);
-}
-
-__global__ __launch_bounds__(TB) void k_reroot_g_narrow(gbp_tree t, const int32_t *__restrict__ order,
-                                                        const uint32_t *__restrict__ first, int64_t r0,
-                                                        int64_t r1) {
-  for (int64_t r = r0; r < r1; r++) {
-    const uint32_t x = first[r] + threadIdx.x;
-    if (x < first[r + 1]) reroot_g(t, order[x]);
-    __syncthreads();  // workgroup-scope release / acquire of the g just written
-  }
-}
-
 __global__ void k_plan_reset(gbp_plan_status *st, int64_t ext_counter, gbp_plan_la *la) {
   *la = gbp_plan_la{};  // no drawn-ahead targets, empty snapshots
   gbp_plan_status z;
@@ -2940,8 +2438,6 @@ __global__ void k_extend_out(const gbp_plan_status *st, int64_t n, const int32_t
     if (new_vertex) new_vertex[i] = eres[i] != GBP_TRAPPED ? evtx[i] : -1;
   }
 }
-
-bool tree_ok(const gbp_tree *t) { return t && t->v && t->count; }
 
 // the target set of half `half` (its parity)
 void select_targets(gbp_plan_ws *w, int32_t half) {
@@ -3374,77 +2870,6 @@ int join_side_streams(gbp_plan_ws *w, hipStream_t s, bool la_used) {
 // ============================================================================
 namespace {
 
-// The tree's capacity-sized allocations, stated once, in allocation order;
-// tree_alloc, gbp_tree_reserve's copies and frees and gbp_tree_destroy all go
-// through this list (count and hm are gbp_tree_create's and
-// gbp_tree_destroy's own).  An allocation holds `parts` sub-arrays of
-// [capacity] rows back to back, so a sub-array's offset depends on the
-// capacity; a reserve carries the first `copied` of them over, the rest is
-// scratch.
-struct TreeArray {
-  size_t row;         // bytes per vertex of one sub-array
-  int parts = 1;
-  int copied = 1;
-  int64_t round = 1;  // rows allocated: the capacity rounded up to a multiple
-  size_t bytes(int64_t cap) const { return row * parts * (size_t)((cap + round - 1) / round * round); }
-  size_t part_offset(int k, int64_t cap) const { return row * k * (size_t)cap; }
-};
-template <class F>
-void for_each_tree_array(F f) {
-  f(&gbp_tree::v, TreeArray{64});
-  f(&gbp_tree::a, TreeArray{80});
-  f(&gbp_tree::g, TreeArray{8});
-  f(&gbp_tree::parent, TreeArray{4});
-  // child | sibling | prev | bfs[2]: the successor lists survive a reserve,
-  // the subtree update's two level queues are scratch
-  f(&gbp_tree::child, TreeArray{4, 5, 3});
-  // the fp16 rows in whole 64-row units (nh_sweep loads a unit's rows past the
-  // tree's end and masks their scores)
-  f(&gbp_tree::vh, TreeArray{2 * NH_ROW, 1, 1, 64});
-}
-
-void tree_free_arrays(gbp_tree *t) {
-  for_each_tree_array([&](auto m, const TreeArray &) {
-    if (t->*m) (void)hipFree(t->*m);
-    t->*m = nullptr;
-  });
-}
-
-// fresh arrays of `cap` rows in *t (what it held before is the caller's to
-// free); on failure nothing is allocated and *t is unchanged
-int tree_alloc(gbp_tree *t, int64_t cap) {
-  gbp_tree n = *t;
-  for_each_tree_array([&](auto m, const TreeArray &) { n.*m = nullptr; });
-  bool ok = true;
-  for_each_tree_array([&](auto m, const TreeArray &A) {
-    if (ok && hipMalloc(&(n.*m), A.bytes(cap)) != hipSuccess) {
-      n.*m = nullptr;
-      ok = false;
-    }
-  });
-  if (!ok) {
-    tree_free_arrays(&n);
-    return GBP_E_ALLOC;
-  }
-  n.sibling = n.child + cap;
-  n.prev = n.child + 2 * cap;
-  n.bfs = n.child + 3 * cap;
-  n.cap = cap;
-  *t = n;
-  return GBP_OK;
-}
-
-template <class T>
-int d2h(T *dst, const T *src, size_t count, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, s));
-  return GBP_OK;
-}
-template <class T>
-int h2d(T *dst, const T *src, size_t count, hipStream_t s) {
-  HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, s));
-  return GBP_OK;
-}
-
 // gbp_tree_append_host / gbp_tree_load_host after their validation: the tree
 // raised to `capacity` rows, the n host rows staged through a buffer of their
 // own and written by `kernel` (k_tree_append / k_tree_load); synchronous
@@ -3707,376 +3132,6 @@ int gbp_tree_device_ptrs(gbp_tree *t, double **states, int32_t **count) {
   if (!tree_ok(t)) return GBP_E_BAD_HANDLE;
   if (states) *states = t->v;
   if (count) *count = t->count;
-  return GBP_OK;
-}
-
-// ---- pruning against a changed terrain ---------------------------
-namespace {
-// stage A's attempt rows in the tree's own grow-only buffer (the call only
-// enqueues: nothing of it may be freed when it returns)
-int prune_rows(gbp_tree *tree, int64_t n, double *&rs, double *&ra) {
-  auto carve = [&](Stage &S) { S.take(rs, 8 * (n - 1)); S.take(ra, 10 * (n - 1)); };
-  const int rc = ensure_ws(&tree->rv, &tree->rv_bytes, stage_bytes_of(carve));
-  return rc ? rc : stage_carve(tree->rv, tree->rv_bytes, carve);
-}
-int prune_args(const gbp_tree *tree, int64_t n, bool arrays) {
-  if (!tree_ok(tree)) return GBP_E_BAD_HANDLE;
-  if (n < 1 || !arrays) return GBP_E_INVALID_ARG;
-  return n > tree->cap ? GBP_E_SHAPE : GBP_OK;
-}
-}  // namespace
-
-int gbp_tree_revalidate_dev(gbp_terrain *t, gbp_tree *tree, int64_t n, int direction, int adaptive,
-                            uint8_t *edge_valid, uint32_t *flags, gbp_stream stream) {
-  if (!t) return GBP_E_BAD_HANDLE;
-  int rc = prune_args(tree, n, edge_valid && flags);
-  if (rc) return rc;
-  if (direction != GBP_FORWARD && direction != GBP_REVERSE) return GBP_E_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
-  if (!t->d_z) return GBP_E_BAD_HANDLE;
-  if (t->device != tree->device) return GBP_E_INVALID_ARG;
-  DeviceGuard g(tree->device);
-  hipStream_t s = (hipStream_t)stream;
-  double *rs = nullptr, *ra = nullptr;
-  if (n > 1 && (rc = prune_rows(tree, n, rs, ra))) return rc;
-  hipLaunchKernelGGL(k_prune_gather, dim3(grid_for((n - 1) * PRUNE_PIECES, TB, t->num_cus * 8)),
-                     dim3(TB), 0, s, *tree, (int32_t)n, (double2 *)rs, (double2 *)ra, edge_valid, flags);
-  HIPCHK(hipGetLastError());
-  if (n == 1) return GBP_OK;
-  // vertex i's decision is row i - 1's: straight into edge_valid[i] / flags[i]
-  return gbp_validate_pairs_dev(t, n - 1, rs, ra, nullptr, direction, adaptive, edge_valid + 1, nullptr,
-                                nullptr, flags + 1, nullptr, stream);
-}
-
-int gbp_tree_prune_dev(gbp_tree *tree, int64_t n, const uint8_t *edge_valid, int32_t *remap,
-                       gbp_prune_stats *stats, gbp_stream stream) {
-  int rc = prune_args(tree, n, edge_valid && remap && stats);
-  if (rc) return rc;
-  int64_t have = 0;
-  if ((rc = gbp_tree_size(tree, &have, stream))) return rc;  // synchronises
-  if (have != n) return GBP_E_SHAPE;
-  DeviceGuard g(tree->device);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t ntile = (n + CB - 1) / CB;
-  DevBuf buf;
-  uint32_t *w[2], *toff;
-  uint2 *tile;
-  rc = stage_buf(buf, [&](Stage &S) {
-    S.take(w[0], n); S.take(w[1], n); S.take(tile, ntile); S.take(toff, ntile);
-  });
-  if (rc) return rc;
-  // the survivors get arrays, a count and search bounds of their own: until
-  // the swap below the tree is untouched, so a failed call leaves it as it was
-  gbp_tree fresh = *tree;
-  if ((rc = tree_alloc(&fresh, tree->cap))) return rc;
-  fresh.count = nullptr;
-  fresh.hm = nullptr;
-  auto drop_fresh = [&]() {
-    tree_free_arrays(&fresh);
-    if (fresh.count) (void)hipFree(fresh.count);
-    if (fresh.hm) (void)hipFree(fresh.hm);
-  };
-  if (hipMalloc(&fresh.count, 4) != hipSuccess || hipMalloc(&fresh.hm, 64) != hipSuccess) {
-    drop_fresh();
-    return GBP_E_ALLOC;
-  }
-  const unsigned gv = grid_for(n, TB, 2048);
-  hipLaunchKernelGGL(k_prune_seed, dim3(gv), dim3(TB), 0, s, tree->parent, edge_valid, (int32_t)n, w[0]);
-  int cur = 0;  // ceil(log2 n) rounds, back to back
-  for (int64_t reach = 1; reach < n; reach <<= 1, cur ^= 1)
-    hipLaunchKernelGGL(k_prune_jump, dim3(gv), dim3(TB), 0, s, w[cur], w[cur ^ 1], (int32_t)n);
-  hipLaunchKernelGGL(k_prune_count, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], edge_valid, (int32_t)n,
-                     tile);
-  hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(CB), 0, s, tile, ntile, toff, (int32_t)n, stats,
-                     fresh.count);
-  hipLaunchKernelGGL(k_prune_rank, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], (int32_t)n, toff, remap);
-  bool ok = hipGetLastError() == hipSuccess && hipMemsetAsync(fresh.hm, 0, 64, s) == hipSuccess;
-  if (ok) {
-    hipLaunchKernelGGL(k_prune_move_rows, dim3(grid_for(n * PRUNE_PIECES, TB, 2048)), dim3(TB), 0, s,
-                       *tree, fresh, (int32_t)n, remap);
-    hipLaunchKernelGGL(k_prune_move_links, dim3(gv), dim3(TB), 0, s, *tree, fresh, (int32_t)n, remap);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) {
-    (void)hipDeviceSynchronize();
-    drop_fresh();
-    return GBP_E_HIP;
-  }
-  tree_free_arrays(tree);
-  (void)hipFree(tree->count);
-  (void)hipFree(tree->hm);
-  *tree = fresh;
-  return GBP_OK;
-}
-
-namespace {
-// The synchronous entries' edge decisions: stage A into dev (edge_valid[n],
-// then flags[n] at byte fl_at: one read-back), the FRAGILE edges re-decided
-// with glibc and edge_valid written back.  dev holds the final decisions and
-// nothing is in flight when this returns.
-int tree_edge_decisions(gbp_terrain *t, gbp_tree *tree, int64_t n, int direction, int adaptive,
-                        uint8_t *dev, size_t fl_at, int64_t *n_resolved, hipStream_t s) {
-  const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
-  uint32_t *dfl = (uint32_t *)(dev + fl_at);
-  int rc = gbp_tree_revalidate_dev(t, tree, n, direction, adaptive, dev, dfl, s);
-  if (rc) return rc;
-  std::vector<uint8_t> dec(dec_bytes);
-  if ((rc = d2h(dec.data(), dev, dec_bytes, s))) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  uint8_t *ev = dec.data();
-  uint32_t *fl = (uint32_t *)(dec.data() + fl_at);
-  bool fragile = false;
-  for (int64_t i = 1; i < n && !fragile; i++) fragile = (fl[i] & GBP_F_FRAGILE) != 0;
-  if (fragile) {
-    // the FRAGILE edges again with glibc, from the rows stage A gathered: the
-    // rows in one copy, the decisions back in one
-    double *rs = nullptr, *ra = nullptr;
-    if ((rc = prune_rows(tree, n, rs, ra))) return rc;  // (the buffer stage A filled)
-    std::vector<double> hs(8 * (n - 1)), ha(10 * (n - 1));
-    if ((rc = d2h(hs.data(), rs, 8 * (n - 1), s))) return rc;
-    if ((rc = d2h(ha.data(), ra, 10 * (n - 1), s))) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    rc = gbp_resolve_fragile_host(t, n - 1, hs.data(), ha.data(), nullptr, direction, adaptive, ev + 1,
-                                  nullptr, nullptr, fl + 1, nullptr, n_resolved);
-    if (!rc) rc = h2d(dev, ev, n, s);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s));  // dec leaves scope only after the copy
-  }
-  return GBP_OK;
-}
-}  // namespace
-
-int gbp_tree_revalidate_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
-                             int32_t *remap, gbp_prune_stats *stats, int64_t *n_resolved) {
-  return gbp_tree_revalidate_keep_host(t, tree, direction, adaptive, remap, nullptr, 0, stats,
-                                       n_resolved);
-}
-
-int gbp_tree_revalidate_keep_host(gbp_terrain *t, gbp_tree *tree, int direction, int adaptive,
-                                  int32_t *remap, int32_t *remap_dev, int64_t remap_cap,
-                                  gbp_prune_stats *stats, int64_t *n_resolved) {
-  if (n_resolved) *n_resolved = 0;
-  if (!t || !tree_ok(tree)) return GBP_E_BAD_HANDLE;
-  if (!stats || (direction != GBP_FORWARD && direction != GBP_REVERSE)) return GBP_E_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
-  if (!t->d_z) return GBP_E_BAD_HANDLE;
-  DeviceGuard g(tree->device);
-  hipStream_t s = t->host_stream;
-  int64_t n = 0;
-  int rc = gbp_tree_size(tree, &n, s);
-  if (rc) return rc;
-  // edge_valid and flags back to back: one read-back
-  const size_t fl_at = ((size_t)n + 255) & ~(size_t)255;
-  const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
-  DevBuf buf;
-  uint8_t *dev;
-  int32_t *dmap;
-  gbp_prune_stats *dst;
-  if (remap_dev && n > remap_cap) return GBP_E_SHAPE;
-  if (remap_dev) {  // the caller keeps the device remap: it must lie on the tree's device
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, remap_dev) != hipSuccess || at.device != tree->device) {
-      (void)hipGetLastError();
-      return GBP_E_INVALID_ARG;
-    }
-  }
-  rc = stage_buf(buf, [&](Stage &S) {
-    S.take(dev, dec_bytes);
-    S.take(dmap, remap_dev ? 0 : n);
-    S.take(dst, 1);
-  });
-  if (rc) return rc;
-  if (remap_dev) dmap = remap_dev;
-  if ((rc = tree_edge_decisions(t, tree, n, direction, adaptive, dev, fl_at, n_resolved, s))) return rc;
-  if ((rc = gbp_tree_prune_dev(tree, n, dev, dmap, dst, s))) return rc;
-  if (remap && (rc = d2h(remap, dmap, n, s))) return rc;
-  if ((rc = d2h(stats, dst, 1, s))) return rc;
-  HIPCHK(hipStreamSynchronize(s));
-  return GBP_OK;
-}
-
-// ---- re-rooting at a vertex ---------------------------------------
-namespace {
-// the last successful gbp_tree_reroot_dev of the process, for gbp_tree_reroot_last
-std::mutex reroot_last_mu;
-double reroot_last_ms[3] = {0, 0, 0};
-int64_t reroot_last_launches = 0;
-// the four marks between the call's three parts; a mark that could not be
-// created or recorded only leaves the times at zero
-struct RerootMarks {
-  hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ok = true;
-  RerootMarks() {
-    for (auto &x : e) ok = hipEventCreate(&x) == hipSuccess && ok;
-  }
-  ~RerootMarks() {
-    for (auto &x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  void mark(int k, hipStream_t s) { ok = ok && hipEventRecord(e[k], s) == hipSuccess; }
-};
-}  // namespace
-
-int gbp_tree_reroot_last(double ms[3], int64_t *launches) {
-  if (!ms || !launches) return GBP_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(reroot_last_mu);
-  for (int k = 0; k < 3; k++) ms[k] = reroot_last_ms[k];
-  *launches = reroot_last_launches;
-  return GBP_OK;
-}
-
-int gbp_tree_reroot_dev(gbp_tree *tree, int64_t n, int32_t new_root, const uint8_t *edge_valid,
-                        int32_t *remap, gbp_reroot_stats *stats, gbp_stream stream) {
-  int rc = prune_args(tree, n, remap && stats);
-  if (rc) return rc;
-  int64_t have = 0;
-  if ((rc = gbp_tree_size(tree, &have, stream))) return rc;  // synchronises
-  if (have != n) return GBP_E_SHAPE;
-  if (new_root < 0 || new_root >= n) return GBP_E_INVALID_ARG;
-  DeviceGuard g(tree->device);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t ntile = (n + CB - 1) / CB;
-  const int32_t k = new_root;
-  DevBuf buf;
-  uint32_t *w[2], *d[2], *toff, *depth, *hist, *first;
-  int32_t *order;
-  uint4 *tile;
-  rc = stage_buf(buf, [&](Stage &S) {
-    S.take(w[0], n); S.take(w[1], n); S.take(d[0], n); S.take(d[1], n); S.take(tile, ntile);
-    S.take(toff, ntile); S.take(depth, n); S.take(hist, n + 1); S.take(first, n + 2); S.take(order, n);
-  });
-  if (rc) return rc;
-  // as in the prune: fresh arrays, count and bounds, swapped in last
-  gbp_tree fresh = *tree;
-  if ((rc = tree_alloc(&fresh, tree->cap))) return rc;
-  fresh.count = nullptr;
-  fresh.hm = nullptr;
-  auto drop_fresh = [&](int code) {
-    (void)hipDeviceSynchronize();
-    tree_free_arrays(&fresh);
-    if (fresh.count) (void)hipFree(fresh.count);
-    if (fresh.hm) (void)hipFree(fresh.hm);
-    return code;
-  };
-  if (hipMalloc(&fresh.count, 4) != hipSuccess || hipMalloc(&fresh.hm, 64) != hipSuccess)
-    return drop_fresh(GBP_E_ALLOC);
-  const unsigned gv = grid_for(n, TB, 2048);
-  RerootMarks marks;
-  int64_t launches = 8;  // seed, count, scan, rank, two moves, levels, order
-  marks.mark(0, s);
-  hipLaunchKernelGGL(k_reroot_seed, dim3(gv), dim3(TB), 0, s, tree->parent, edge_valid, (int32_t)n, k, w[0],
-                     d[0]);
-  int cur = 0;  // ceil(log2 n) rounds, back to back
-  for (int64_t reach = 1; reach < n; reach <<= 1, cur ^= 1, launches++)
-    hipLaunchKernelGGL(k_reroot_jump, dim3(gv), dim3(TB), 0, s, w[cur], d[cur], w[cur ^ 1], d[cur ^ 1],
-                       (int32_t)n);
-  marks.mark(1, s);
-  hipLaunchKernelGGL(k_reroot_count, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], d[cur], edge_valid,
-                     (int32_t)n, k, tile);
-  hipLaunchKernelGGL(k_reroot_scan, dim3(1), dim3(CB), 0, s, tile, ntile, toff, (int32_t)n, stats,
-                     fresh.count);
-  bool ok = hipGetLastError() == hipSuccess && hipMemsetAsync(fresh.hm, 0, 64, s) == hipSuccess &&
-            hipMemsetAsync(hist, 0, (n + 1) * sizeof(uint32_t), s) == hipSuccess;
-  if (!ok) return drop_fresh(GBP_E_HIP);
-  hipLaunchKernelGGL(k_reroot_rank, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], d[cur], (int32_t)n, k,
-                     toff, remap, depth, hist);
-  // the prune's move: k's old parent is not kept, so parent[0] = -1 and the
-  // new root is in no list; the g copied here is written again below
-  hipLaunchKernelGGL(k_prune_move_rows, dim3(grid_for(n * PRUNE_PIECES, TB, 2048)), dim3(TB), 0, s, *tree,
-                     fresh, (int32_t)n, remap);
-  hipLaunchKernelGGL(k_prune_move_links, dim3(gv), dim3(TB), 0, s, *tree, fresh, (int32_t)n, remap);
-  hipLaunchKernelGGL(k_reroot_levels, dim3(1), dim3(CB), 0, s, hist, stats, first, fresh.a);
-  hipLaunchKernelGGL(k_reroot_order, dim3(gv), dim3(TB), 0, s, depth, fresh.count, first, hist, order);
-  marks.mark(2, s);
-  if (hipGetLastError() != hipSuccess) return drop_fresh(GBP_E_HIP);
-  // the levels' sizes decide the launches of g
-  gbp_reroot_stats hs;
-  if (d2h(&hs, stats, 1, s) || hipStreamSynchronize(s) != hipSuccess) return drop_fresh(GBP_E_HIP);
-  const int64_t nl = hs.depth + 1;
-  if (hs.n_kept < 1 || hs.n_kept > n || nl < 1 || nl > hs.n_kept) return drop_fresh(GBP_E_HIP);
-  std::vector<uint32_t> lv(nl + 1);
-  if (d2h(lv.data(), first, nl + 1, s) || hipStreamSynchronize(s) != hipSuccess)
-    return drop_fresh(GBP_E_HIP);
-  for (int64_t r = 0; r < nl; launches++) {
-    if (lv[r + 1] - lv[r] > (uint32_t)TB) {
-      hipLaunchKernelGGL(k_reroot_g_wide, dim3(grid_for(lv[r + 1] - lv[r], TB, 2048)), dim3(TB), 0, s, fresh,
-                         order, (int64_t)lv[r], (int64_t)lv[r + 1]);
-      r++;
-      continue;
-    }
-    int64_t e = r + 1;  // a run of levels no wider than a workgroup
-    while (e < nl && lv[e + 1] - lv[e] <= (uint32_t)TB) e++;
-    hipLaunchKernelGGL(k_reroot_g_narrow, dim3(1), dim3(TB), 0, s, fresh, order, first, r, e);
-    r = e;
-  }
-  marks.mark(3, s);
-  ok = hipGetLastError() == hipSuccess;
-  if (hipStreamSynchronize(s) != hipSuccess || !ok) return drop_fresh(GBP_E_HIP);
-  {
-    std::lock_guard<std::mutex> lk(reroot_last_mu);
-    for (int q = 0; q < 3; q++) {
-      float t = 0.f;
-      reroot_last_ms[q] = marks.ok && hipEventElapsedTime(&t, marks.e[q], marks.e[q + 1]) == hipSuccess ? t : 0.0;
-    }
-    reroot_last_launches = launches;
-  }
-  tree_free_arrays(tree);
-  (void)hipFree(tree->count);
-  (void)hipFree(tree->hm);
-  *tree = fresh;
-  return GBP_OK;
-}
-
-int gbp_tree_reroot_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, int direction,
-                         int adaptive, int32_t *remap, gbp_reroot_stats *stats, int64_t *n_resolved) {
-  return gbp_tree_reroot_keep_host(t, tree, new_root, direction, adaptive, remap, nullptr, 0, stats,
-                                   n_resolved);
-}
-
-int gbp_tree_reroot_keep_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, int direction,
-                              int adaptive, int32_t *remap, int32_t *remap_dev, int64_t remap_cap,
-                              gbp_reroot_stats *stats, int64_t *n_resolved) {
-  if (n_resolved) *n_resolved = 0;
-  if (!tree_ok(tree)) return GBP_E_BAD_HANDLE;
-  if (!stats || (t && direction != GBP_FORWARD && direction != GBP_REVERSE)) return GBP_E_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
-  if (t && !t->d_z) return GBP_E_BAD_HANDLE;
-  DeviceGuard g(tree->device);
-  hipStream_t s = t ? t->host_stream : nullptr;
-  int64_t n = 0;
-  int rc = gbp_tree_size(tree, &n, s);
-  if (rc) return rc;
-  if (new_root < 0 || new_root >= n) return GBP_E_INVALID_ARG;
-  const size_t fl_at = ((size_t)n + 255) & ~(size_t)255;
-  const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
-  DevBuf buf;
-  uint8_t *dev;
-  int32_t *dmap;
-  gbp_reroot_stats *dst;
-  if (remap_dev && n > remap_cap) return GBP_E_SHAPE;
-  if (remap_dev) {  // the caller keeps the device remap: it must lie on the tree's device
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, remap_dev) != hipSuccess || at.device != tree->device) {
-      (void)hipGetLastError();
-      return GBP_E_INVALID_ARG;
-    }
-  }
-  rc = stage_buf(buf, [&](Stage &S) {
-    S.take(dev, dec_bytes);
-    S.take(dmap, remap_dev ? 0 : n);
-    S.take(dst, 1);
-  });
-  if (rc) return rc;
-  if (remap_dev) dmap = remap_dev;
-  if (t && (rc = tree_edge_decisions(t, tree, n, direction, adaptive, dev, fl_at, n_resolved, s)))
-    return rc;
-  if ((rc = gbp_tree_reroot_dev(tree, n, new_root, t ? dev : nullptr, dmap, dst, s))) return rc;
-  if (remap && (rc = d2h(remap, dmap, n, s))) return rc;
-  if ((rc = d2h(stats, dst, 1, s))) return rc;
-  HIPCHK(hipStreamSynchronize(s));
   return GBP_OK;
 }
 

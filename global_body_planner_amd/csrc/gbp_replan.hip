@@ -4,7 +4,9 @@
 // (gbp_plan_shared_read_host / _load_host / _remap_dev), and the joined path
 // of two device trees extracted without reading the trees
 // (gbp_tree_path_dev / _host).  A translation unit of its own: the objects of
-// gbp_engine.hip, gbp_plan.hip and gbp_terrain.hip do not depend on it.
+// gbp_engine.hip, gbp_plan.hip, gbp_tree_maint.hip and gbp_terrain.hip do not
+// depend on it.  The handles, tree_ok and the block sizes WAVE / TB / CB:
+// gbp_internal.h.
 //
 // The list is gbp_plan_ws::sshared, pairs (a, b) of a vertex of Ta and one of
 // Tb in the order stage 5's append listed them; its length is the status's
@@ -15,26 +17,19 @@
 // is taken with k_star_rank's rule (NaN skipped, strictly cheaper, ties to
 // the earliest).
 //
-// The remap's compaction is the prune's: tiles of 1,024 pairs count their
-// kept pairs with wave ballots, one workgroup scans the tiles' counts, every
-// tile ranks its pairs again from its offset and writes them into a second
-// buffer, which is then copied over the list (compacting in place would let a
-// tile overwrite pairs another tile has not read).  No workgroup waits for
-// another.  The list's length is read on the device, so the grids are sized
-// from the number of CUs and walk the tiles with a stride.
+// The remap's compaction is gbp_compact.h's, over tiles of 1,024 pairs; the
+// ranked pairs go into a second buffer, which is then copied over the list
+// (compacting in place would let a tile overwrite pairs another tile has not
+// read).  The list's length is read on the device, so the grids are sized from
+// the number of CUs and walk the tiles with a stride.
 #pragma clang fp contract(off)
 
 #include <cmath>
 
+#include "gbp_compact.h"
 #include "gbp_internal.h"
 
 namespace {
-
-constexpr int WAVE = 64;
-constexpr int TB = 256;   // threads of the grid-stride kernels and of the path kernel
-constexpr int CB = 1024;  // pairs per tile (= threads of the tile kernels)
-
-bool tree_ok(const gbp_tree *t) { return t && t->v && t->count; }
 
 // what the new index of a listed vertex is (NULL remap: the identity)
 __device__ __forceinline__ int32_t remapped(const int32_t *__restrict__ remap, int32_t i) {
@@ -70,37 +65,24 @@ __device__ __forceinline__ int64_t list_len(const gbp_plan_status *st, int64_t m
   return n < 0 ? 0 : (n > max_shared ? max_shared : n);
 }
 
-// tile t: x = kept pairs, y = lost with a, z = lost with b alone
+// tile t: [0] kept pairs, [1] lost with a, [2] lost with b alone, [3] an index
+// outside its tree
+using PairTile = TileRec<4>;
+
 __global__ __launch_bounds__(CB) void k_shared_count(const gbp_plan_status *__restrict__ st,
                                                      int64_t max_shared,
                                                      const int2 *__restrict__ list,
                                                      const int32_t *__restrict__ remap_a, int64_t n_a,
                                                      const int32_t *__restrict__ remap_b, int64_t n_b,
-                                                     uint4 *__restrict__ tile,
+                                                     PairTile *__restrict__ tile,
                                                      gbp_shared_stats *__restrict__ ctl) {
-  __shared__ uint32_t sk[CB / WAVE], sa[CB / WAVE], sb[CB / WAVE], sx[CB / WAVE];
   const int64_t n = list_len(st, max_shared), ntile = (n + CB - 1) / CB;
   for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
     const PairFate f = pair_fate(list, t * CB + threadIdx.x, n, remap_a, n_a, remap_b, n_b);
-    const unsigned long long mk = __ballot(f.keep), ma = __ballot(f.lost_a), mb = __ballot(f.lost_b),
-                             mx = __ballot(f.bad);
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-      sk[threadIdx.x / WAVE] = (uint32_t)__popcll(mk);
-      sa[threadIdx.x / WAVE] = (uint32_t)__popcll(ma);
-      sb[threadIdx.x / WAVE] = (uint32_t)__popcll(mb);
-      sx[threadIdx.x / WAVE] = (uint32_t)__popcll(mx);
-    }
-    __syncthreads();
+    const PairTile c = tile_count<4>({f.keep, f.lost_a, f.lost_b, f.bad});
     if (threadIdx.x == 0) {
-      uint32_t k = 0, a = 0, b = 0, x = 0;
-      for (int q = 0; q < CB / WAVE; q++) {
-        k += sk[q];
-        a += sa[q];
-        b += sb[q];
-        x += sx[q];
-      }
-      tile[t] = make_uint4(k, a, b, x);
-      if (x) atomicOr((unsigned long long *)&ctl->error, 1ull);
+      tile[t] = c;
+      if (c.c[3]) atomicOr((unsigned long long *)&ctl->error, 1ull);
     }
     __syncthreads();
   }
@@ -108,46 +90,17 @@ __global__ __launch_bounds__(CB) void k_shared_count(const gbp_plan_status *__re
 
 // one workgroup: toff[t] = the kept pairs of the tiles before t; the record
 __global__ __launch_bounds__(CB) void k_shared_scan(const gbp_plan_status *__restrict__ st,
-                                                    int64_t max_shared, const uint4 *__restrict__ tile,
+                                                    int64_t max_shared,
+                                                    const PairTile *__restrict__ tile,
                                                     uint32_t *__restrict__ toff,
                                                     gbp_shared_stats *__restrict__ ctl) {
-  __shared__ uint32_t ws[CB / WAVE], wa[CB / WAVE], wb[CB / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const int64_t n = list_len(st, max_shared), ntile = (n + CB - 1) / CB;
-  uint32_t run = 0, la = 0, lb = 0;  // the same in every thread
-  for (int64_t base = 0; base < ntile; base += CB) {
-    const int64_t t = base + threadIdx.x;
-    const uint4 c = t < ntile ? tile[t] : make_uint4(0u, 0u, 0u, 0u);
-    uint32_t incl = c.x, asum = c.y, bsum = c.z;  // inclusive scan / sums over the wave
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, WAVE);
-      if (lane >= d) incl += up;
-      asum += __shfl_xor(asum, d, WAVE);
-      bsum += __shfl_xor(bsum, d, WAVE);
-    }
-    if (lane == WAVE - 1) ws[wv] = incl;
-    if (lane == 0) {
-      wa[wv] = asum;
-      wb[wv] = bsum;
-    }
-    __syncthreads();
-    uint32_t woff = 0, tot = 0;
-    for (int q = 0; q < CB / WAVE; q++) {
-      if (q < wv) woff += ws[q];
-      tot += ws[q];
-      la += wa[q];
-      lb += wb[q];
-    }
-    if (t < ntile) toff[t] = run + woff + incl - c.x;
-    run += tot;
-    __syncthreads();
-  }
+  const PairTile tot = tile_scan<4>([tile](int64_t t) { return tile[t]; }, ntile, 0u, toff);
   if (threadIdx.x == 0) {
     ctl->n_before = n;
-    ctl->n_kept = run;
-    ctl->n_dropped_a = la;
-    ctl->n_dropped_b = lb;
+    ctl->n_kept = tot.c[0];
+    ctl->n_dropped_a = tot.c[1];
+    ctl->n_dropped_b = tot.c[2];
   }
 }
 
@@ -161,18 +114,12 @@ __global__ __launch_bounds__(CB) void k_shared_move(const gbp_plan_status *__res
                                                     int2 *__restrict__ list2,
                                                     const gbp_shared_stats *__restrict__ ctl) {
   if (ctl->error) return;  // an index outside its tree: the list stays as it is
-  __shared__ uint32_t sk[CB / WAVE];
-  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const int64_t n = list_len(st, max_shared), ntile = (n + CB - 1) / CB;
   for (int64_t t = blockIdx.x; t < ntile; t += gridDim.x) {
     const PairFate f = pair_fate(list, t * CB + threadIdx.x, n, remap_a, n_a, remap_b, n_b);
-    const unsigned long long m = __ballot(f.keep);
-    if (lane == 0) sk[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    uint32_t off = toff[t];
-    for (int q = 0; q < wv; q++) off += sk[q];
-    // off + rank < n_kept <= n <= max_shared: inside the second buffer
-    if (f.keep) list2[off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = make_int2(f.ra, f.rb);
+    const uint32_t at = tile_rank(f.keep, toff[t]);
+    // at < n_kept <= n <= max_shared: inside the second buffer
+    if (f.keep) list2[at] = make_int2(f.ra, f.rb);
     __syncthreads();
   }
 }
@@ -334,7 +281,7 @@ __global__ __launch_bounds__(TB) void k_tree_path(gbp_tree A, int32_t ia, gbp_tr
 // ---- host side ----------------------------------------------------------------
 struct Scratch {
   int2 *list2 = nullptr;
-  uint4 *tile = nullptr;
+  PairTile *tile = nullptr;
   uint32_t *toff = nullptr;
   gbp_shared_stats *ctl = nullptr;
 };

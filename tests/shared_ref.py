@@ -2,8 +2,8 @@
 of two trees, restated in numpy: the expected values of
 test_gpu_shared_remap.py, test_gpu_tree_path.py and test_gpu_replan_session.py
 (checked on their own in test_shared_ref.py).  Nothing here is the engine's:
-the remap is boolean indexing, the ranking a loop in list order, the join two
-parent walks.  Also the small trees and pair lists those tests share."""
+the remap is boolean indexing, the ranking the first minimum in list order
+(vectorised: the lists reach a million pairs), the join two parent walks.  Also the small trees and pair lists those tests share."""
 import functools
 
 import numpy as np
@@ -34,12 +34,13 @@ def rank(pairs, ga, gb):
     (rrt_star_connect.cpp:181-193): in list order, a NaN cost skipped, a pair
     taken only when strictly cheaper, so ties stay with the earliest; (-1, -1,
     inf) when nothing is taken."""
-    best = (-1, -1, np.inf)
-    for a, b in np.asarray(pairs, np.int64).reshape(-1, 2):
-        c = ga[a] + gb[b]          # NaN < x is False: skipped
-        if c < best[2]:
-            best = (int(a), int(b), float(c))
-    return best
+    p = np.asarray(pairs, np.int64).reshape(-1, 2)
+    c = np.asarray(ga, np.float64)[p[:, 0]] + np.asarray(gb, np.float64)[p[:, 1]]
+    c = np.where(c < np.inf, c, np.inf)   # NaN < x is False: skipped, like a cost of inf
+    if len(c) == 0 or not c.min() < np.inf:
+        return (-1, -1, np.inf)
+    i = int(np.argmin(c))                 # the first of equal minima: the earliest
+    return (int(p[i, 0]), int(p[i, 1]), float(c[i]))
 
 
 def chain(parent, i):

@@ -90,6 +90,43 @@ def _tree_with_g(tree, keep):
     return dt, g
 
 
+# ---- 1b: more tiles than one pass of the tile scan ----------------------------------------------
+def test_more_than_1024_tiles(gpu):
+    """1,024 x 1,024 + 1 pairs are 1,025 tiles: the one workgroup that scans
+    the tiles' counts takes a second pass, with one tile in it, and the tiles
+    after the first 1,024 get offsets that carry the first pass's total.  Two
+    trees of 64 vertices, the pairs drawn with repeats; each remap drops a few
+    vertices.  A workspace of its own with room for the list (max_shared
+    1 << 22)."""
+    n = 1024 * 1024 + 1
+    T = device_terrain(None)
+    ws = engine.PlanWorkspace(T, 256)
+    ws.star_config(3.0, 1 << 12)
+    ws.reset()
+    A, B = SR.small_tree(21, 64), SR.small_tree(22, 64)
+    trees = []
+    for t in (A, B):
+        dt = engine.DeviceTree(t["v"][0], capacity=64)
+        dt.load(t["v"], t["act"], t["parent"])
+        assert np.array_equal(bits(dt.read()[3]), bits(t["g"]))
+        trees.append(dt)
+    ta, tb = trees
+    rng = np.random.default_rng(1000 + n)
+    pairs = SR.random_pairs(rng, n, 64, 64)
+    ws.shared_load(ta, tb, pairs)
+    assert_state(ws, pairs, SR.rank(pairs, A["g"], B["g"]), ("loaded", n))
+    ra, rb = SR.random_remap(rng, 64, keep=0.9), SR.random_remap(rng, 64, keep=0.9)
+    assert 0 < (ra < 0).sum() < 16 and 0 < (rb < 0).sum() < 16
+    want, wstats = SR.remap_pairs(pairs, ra, rb)
+    ta2, tb2 = _tree_with_g(A, ra >= 0), _tree_with_g(B, rb >= 0)
+    stats = ws.shared_remap(ta2[0], tb2[0], ra, rb)
+    assert {k: stats[k] for k in SR.STATS} == {k: wstats[k] for k in SR.STATS}, (stats, wstats)
+    assert stats["error"] == 0
+    assert 0 < wstats["n_kept"] < n and wstats["n_dropped_a"] and wstats["n_dropped_b"]
+    assert wstats["n_kept"] > 1024 * 1024 // 2   # kept pairs on both sides of the passes' boundary
+    assert_state(ws, want, SR.rank(want, ta2[1], tb2[1]), ("remapped", n))
+
+
 # ---- 2: the identity ----------------------------------------------------------------------------
 def test_both_remaps_null_is_the_identity(gpu):
     ws, ta, tb, A, B = setup()

@@ -1,6 +1,6 @@
 """Device trees pruned against a changed terrain (gbp_tree_revalidate_dev /
-gbp_tree_prune_dev / gbp_tree_revalidate_host, csrc/gbp_plan.hip) against the
-numpy restatement in tests/prune_ref.py, bit for bit: the remap, the four
+gbp_tree_prune_dev / gbp_tree_revalidate_host, csrc/gbp_tree_maint.hip) against
+the numpy restatement in tests/prune_ref.py, bit for bit: the remap, the four
 counters, and v / a / parent / g of the pruned tree.
 
 The trees are the oracle's (tests/prune_ref.py: set S, RRT*-Connect with

@@ -1,5 +1,5 @@
 """Device trees re-rooted at one of their vertices (gbp_tree_reroot_dev /
-gbp_tree_reroot_host, csrc/gbp_plan.hip) against the numpy restatement in
+gbp_tree_reroot_host, csrc/gbp_tree_maint.hip) against the numpy restatement in
 tests/reroot_ref.py, bit for bit: the remap, the six counters, and v / a /
 parent / g of the re-rooted tree; the successor lists are read back and must
 hold exactly each vertex's children.
@@ -20,8 +20,8 @@ from global_body_planner_amd import engine, planner
 from tests import prune_ref as R
 from tests import reroot_ref as RR
 from tests.helpers import bits, same_f64
-from tests.test_gpu_tree_prune import (assert_lists_hold_the_children, assert_same_tree,
-                                       device_terrain)
+from tests.test_gpu_tree_prune import (assert_lists_hold_the_children, assert_prune_equals,
+                                       assert_same_tree, device_terrain)
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +130,57 @@ def test_several_tiles(gpu, permute):
     assert_reroot_equals(dev, ref, ("tiles", permute))
     # the whole tree too: every level, the widest ones included
     assert_reroot_equals(device_reroot(tree, 0), RR.reroot(tree, 0), ("tiles, whole", permute))
+
+
+# ---- 4b: the prune is a re-root at the root -------------------------------------------------
+def test_prune_equals_a_reroot_at_the_root(gpu):
+    """gbp_tree_prune_dev and gbp_tree_reroot_dev(new_root = 0) are one
+    pipeline: on the same tree and the same edge decisions they write the same
+    remap, tree and counters.  2,051 vertices (two full compaction tiles and a
+    tile of 3) of a random recursive tree, renumbered so that parents follow
+    their children; about one edge in ten fails, drawn at random."""
+    import torch
+    from global_body_planner_amd.engine import _ptr, _stream
+    lib = L.load()
+    n = 2051
+    tree, k = RR.permuted(RR.random_recursive_tree(n, seed=20261022), 0, 20261023)
+    assert k == 0 and np.any(tree["parent"] > np.arange(n))
+    ok = (np.random.default_rng(20261024).random(n) >= 0.1).astype(np.uint8)
+    assert 0.05 < 1.0 - ok.mean() < 0.15
+    ref_p = R.prune(dict(tree, g=RR.derive_g(tree["v"], tree["parent"])), ok)
+    ref_r = RR.reroot(tree, 0, ok)
+    share = ref_p[2]["n_kept"] / n
+    assert 0.0 < share < 1.0
+    assert np.any(np.diff(np.flatnonzero(ref_p[1] < 0)) > 1)   # not one contiguous run
+    T = device_terrain(None)
+    dev = T.torch_device
+    s = _stream(T.device)
+    ev = torch.from_numpy(ok).to(dev)
+    got = []
+    for reroot in (False, True):
+        dt = loaded(tree)
+        remap = torch.full((n,), 7, dtype=torch.int32, device=dev)
+        st = torch.full((6 if reroot else 4,), -1, dtype=torch.int64, device=dev)
+        if reroot:
+            rc = lib.gbp_tree_reroot_dev(dt._h, n, 0, _ptr(ev), _ptr(remap), _ptr(st), s)
+        else:
+            rc = lib.gbp_tree_prune_dev(dt._h, n, _ptr(ev), _ptr(remap), _ptr(st), s)
+        assert rc == 0
+        sv, sa, sp, sg = dt.read()
+        assert_lists_hold_the_children(dt, sp)
+        names = RR.STATS if reroot else ("n_before", "n_kept", "n_edge_invalid", "n_inherited")
+        got.append((dict(v=sv, act=sa, parent=sp, g=sg), remap.cpu().numpy(),
+                    dict(zip(names, st.cpu().tolist()))))
+    (ptree, premap, pstats), (rtree, rremap, rstats) = got
+    assert np.array_equal(premap, rremap), np.flatnonzero(premap != rremap)[:10]
+    assert_same_tree(ptree, rtree, "prune against re-root at 0")
+    for name in ("n_before", "n_kept", "n_edge_invalid", "n_inherited"):
+        assert pstats[name] == rstats[name], (name, pstats, rstats)
+    assert rstats["n_outside"] == 0
+    assert rstats["depth"] == ref_r[2]["depth"]
+    assert_prune_equals(got[0], ref_p, "prune")
+    assert_reroot_equals(got[1], ref_r, "re-root at 0")
+    print(f"prune = re-root at 0: {pstats}, depth {rstats['depth']}")
 
 
 # ---- 5: depth -------------------------------------------------------------------------------
