@@ -1,11 +1,18 @@
-// gbp_compact.h — the pieces of the order-preserving compaction without a wait
+// gbp_compact.h — the order-preserving compactions.  Device only; not part of
+// the C ABI.
+//
+// The look-back form, one launch (ordered_rank, at the end of this file): the
+// workgroups chain their counts with a decoupled look-back.  The planner's
+// appends (gbp_plan.hip) and the targets drawn inside a search (gbp_nn.hip)
+// use it; RRT*'s item counts (gbp_star.hip) are published as its tile words.
+//
+// The two-pass form, the pieces of the compaction without a wait
 // between workgroups, for workgroups of CB threads: a tile of CB
 // elements counts its kept elements with wave ballots (tile_count), one
 // workgroup scans the tiles' counts (tile_scan), then every tile ranks its
 // elements again from its offset, from the same ballots (tile_rank).  The
 // prune and the re-root of a device tree (gbp_tree_maint.hip) and the remap of
-// RRT*'s kept connections (gbp_replan.hip) are built from them.  Device only;
-// not part of the C ABI.
+// RRT*'s kept connections (gbp_replan.hip) are built from them.
 //
 // A tile's record holds K 32-bit components: [0] the kept elements, which the
 // scan turns into offsets, then side sums; with MAXLAST the last component is a
@@ -112,4 +119,72 @@ __device__ __forceinline__ uint32_t tile_rank(bool keep, uint32_t off) {
   __syncthreads();
   for (int q = 0; q < wv; q++) off += sk[q];
   return off + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+}
+
+constexpr uint32_t LOOKBACK_SPIN_LIMIT = 1u << 24;
+
+// ---- ordered compaction across the grid ---------------------------------------
+// Block b of a CB-thread grid keeps the items whose `keep` is set; returns the
+// item's rank among all kept items of the grid (blocks in order, threads in
+// order within a block).  Tile states are 64-bit words (epoch | flag | count),
+// published and polled with agent-scope atomic RMW operations (executed at
+// memory, coherent across the XCDs' L2s).  Every block of the grid must call
+// this exactly once.  The grid must be resident at once (callers launch at
+// most a few hundred 1024-thread blocks).  *total gets the grid's total
+// (written by the last block).
+__device__ __forceinline__ unsigned long long tile_word(uint32_t epoch, uint32_t flag, uint32_t v) {
+  return ((unsigned long long)epoch << 32) | ((unsigned long long)flag << 30) | (v & 0x3FFFFFFFu);
+}
+
+static __device__ uint32_t ordered_rank(bool keep, unsigned long long *tiles, uint32_t epoch,
+                                        int32_t *total, gbp_plan_status *st, uint32_t tile,
+                                        uint32_t ntile) {
+  __shared__ uint32_t wsum[CB / WAVE];
+  __shared__ uint32_t s_excl;
+  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
+  const unsigned long long m = __ballot(keep);
+  const uint32_t wr = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+  if (lane == 0) wsum[w] = (uint32_t)__popcll(m);
+  __syncthreads();
+  uint32_t woff = 0, bsum = 0;
+  for (int i = 0; i < (int)(blockDim.x / WAVE); i++) {
+    if (i < w) woff += wsum[i];
+    bsum += wsum[i];
+  }
+  if (threadIdx.x == 0) {
+    const uint32_t b = tile;
+    uint32_t excl = 0;
+    if (b > 0) {
+      __hip_atomic_exchange(&tiles[b], tile_word(epoch, 1, bsum), __ATOMIC_RELAXED,
+                            __HIP_MEMORY_SCOPE_AGENT);
+      int j = (int)b - 1;
+      uint32_t spins = 0;
+      for (;;) {
+        const unsigned long long x =
+            __hip_atomic_fetch_add(&tiles[j], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t flag = (uint32_t)(x >> 30) & 3u;
+        if ((uint32_t)(x >> 32) != epoch || flag == 0) {
+          if (++spins > LOOKBACK_SPIN_LIMIT) {  // bounded: report, never hang
+            atomicOr(&st->error, 1u);
+            break;
+          }
+          __builtin_amdgcn_s_sleep(2);
+          continue;
+        }
+        excl += (uint32_t)(x & 0x3FFFFFFFu);
+        if (flag == 2 || j == 0) break;
+        --j;
+      }
+    }
+    __hip_atomic_exchange(&tiles[b], tile_word(epoch, 2, excl + bsum), __ATOMIC_RELAXED,
+                          __HIP_MEMORY_SCOPE_AGENT);
+    s_excl = excl;
+    if (b == ntile - 1) *total = (int32_t)(excl + bsum);
+  }
+  __syncthreads();
+  return s_excl + woff + wr;
+}
+__device__ __forceinline__ uint32_t ordered_rank(bool keep, unsigned long long *tiles, uint32_t epoch,
+                                                 int32_t *total, gbp_plan_status *st) {
+  return ordered_rank(keep, tiles, epoch, total, st, blockIdx.x, gridDim.x);
 }

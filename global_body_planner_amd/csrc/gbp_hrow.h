@@ -1,5 +1,5 @@
 // gbp_hrow.h — a vertex's row of the fp16 split rows the matrix-core
-// nearest-neighbour search reads (gbp_plan.hip, "nearest neighbour in a device
+// nearest-neighbour search reads (gbp_nn.hip, "nearest neighbour in a device
 // tree on the matrix cores": the layout's use and its error bounds), shared
 // with the kernels that write rows outside the planner loop
 // (gbp_tree_maint.hip's move).  Not part of the C ABI.

@@ -1,6 +1,9 @@
 // gbp_internal.h — definitions shared by the engine's translation units
 // (gbp_engine.hip: terrain, lookups, pair checks, samplers, extend, NN;
-// gbp_plan.hip: device trees and the device-resident planner loop;
+// gbp_plan.hip: the device-resident planner loop's half-iteration and its
+// workspace; gbp_nn.hip: the nearest-neighbour search in a device tree;
+// gbp_star.hip: RRT*'s insertion; gbp_shortcut.hip: the connect table of
+// found paths; gbp_tree.hip: the device tree handle;
 // gbp_tree_maint.hip: a device tree pruned against a changed terrain or
 // re-rooted at one of its vertices;
 // gbp_terrain.hip: a handle's heights updated in place and its host mirror;
@@ -222,7 +225,8 @@ int stage_buf(DevBuf &b, F carve) {
 }
 
 // ============================================================================
-// the planner's handles (gbp_plan.hip creates, fills and frees them;
+// the planner's handles (gbp_tree.hip creates, fills and frees the trees,
+// gbp_plan.hip the workspace, whose RRT* block is gbp_star.hip's;
 // gbp_tree_maint.hip replaces a tree's arrays; gbp_replan.hip reads the trees
 // and the kept connections)
 // ============================================================================
@@ -253,6 +257,11 @@ inline bool tree_ok(const gbp_tree *t) { return t && t->v && t->count; }
 __device__ __forceinline__ void copy8(double *d, const double *s) {
 #pragma unroll
   for (int k = 0; k < 8; k++) d[k] = s[k];
+}
+
+__device__ __forceinline__ void copy10(double *d, const double *s) {
+#pragma unroll
+  for (int k = 0; k < 10; k++) d[k] = s[k];
 }
 
 // The tree's capacity-sized allocations, stated once, in allocation order;
@@ -342,6 +351,26 @@ struct NsBuf {
   int2 *qh;                 // [bmax] a query's first entry and its entries
 };
 
+// the search's share of the planner workspace (gbp_plan_ws::nnw): sized by
+// nn_ws_init, carved from the workspace's block by nn_ws_carve, its counters
+// zeroed by nn_ws_zero (gbp_nn.h)
+struct NnWs {
+  int stats = 0;               // GBP_OPT_NN_STATS: k_nn_hreduce counts its re-checks in the status
+  int items = 4096;            // matrix-core search: work items (= waves) per launch
+  // the partials: NN_MAX_CHUNKS * bmax slots, pd[c * nq + qi]
+  // (d2 / i2: the look-ahead search's, on its own stream)
+  double *d = nullptr, *d2 = nullptr;
+  int32_t *i = nullptr, *i2 = nullptr;
+  // the direct search for a few queries (k_nn_small): per-workgroup partials
+  // and the completion count of its last-workgroup reduce
+  double *ns_d = nullptr;
+  int32_t *ns_i = nullptr;
+  uint32_t *ns_fin = nullptr;
+  int ns_grid = 1;             // its workgroups (one per CU of an XCD)
+  int64_t ns_capq = 0;         // queries its partials hold (ns_grid x ns_capq slots)
+  NsBuf nsb[2] = {};           // k_nn_scan's lists: the caller's stream, the look-ahead's
+};
+
 // the look-ahead search's device state (gbp_plan_ws::la), by half % 3 (the
 // drawn-ahead target sets) and by parity (the searched trees' snapshots)
 struct gbp_plan_la {
@@ -359,8 +388,6 @@ struct gbp_plan_ws {
   unsigned long long *tiles = nullptr;  // look-back tile states
   uint32_t epoch = 0;          // per-compaction tag of the tile states
   uint64_t seq = 0;            // launch sequence number of the planner kernels (gated())
-  int nn_stats = 0;            // GBP_OPT_NN_STATS: k_nn_hreduce counts its re-checks in the status
-  int nn_items = 4096;         // matrix-core search: work items (= waves) per launch
   int64_t ntiles = 0;
   // stage 0-1: three sets, by half % 3 (with the look-ahead search, half
   // h + 2's targets are drawn while half h + 1's are searched and half h
@@ -397,18 +424,7 @@ struct gbp_plan_ws {
   double *ksn = nullptr;       // [bmax][8]
   double *kan = nullptr;       // [bmax][10]
   uint32_t *kf = nullptr;      // [bmax] connect flags
-  // nearest-neighbour partials: NN_MAX_CHUNKS * bmax slots, pd[c * nq + qi]
-  // (nn_d2 / nn_i2: the look-ahead search's, on its own stream)
-  double *nn_d = nullptr, *nn_d2 = nullptr;
-  int32_t *nn_i = nullptr, *nn_i2 = nullptr;
-  // the direct search for a few queries (k_nn_small): per-workgroup partials
-  // and the completion count of its last-workgroup reduce
-  double *ns_d = nullptr;
-  int32_t *ns_i = nullptr;
-  uint32_t *ns_fin = nullptr;
-  int ns_grid = 1;             // its workgroups (one per CU of an XCD)
-  int64_t ns_capq = 0;         // queries its partials hold (ns_grid x ns_capq slots)
-  NsBuf nsb[2] = {};           // k_nn_scan's lists: the caller's stream, the look-ahead's
+  NnWs nnw;                    // the searches' partials, lists and knobs (gbp_nn.hip)
   // the look-ahead search (gbp_plan_halves_dev): half h + 1's targets drawn
   // and searched on la_stream while half h's extends, connects and appends
   // run on the caller's stream (la_go: main -> side, la_done: side -> main)
@@ -471,9 +487,30 @@ struct gbp_plan_ws {
   size_t replan_bytes = 0;
 };
 
+// a function one translation unit defines for another: never exported
+#define GBP_INTERNAL __attribute__((visibility("hidden")))
+
 // the device's look-ahead stream of the planner loop (created once per
 // process and device; null on failure); gbp_plan.hip
 hipStream_t gbp_internal_la_stream(int device, int num_cus);
+
+// RRT*'s part of a half-iteration, enqueued by gbp_plan.hip's enqueue_stages
+// (gbp_star.hip; th: the half's timing slot or null).  Stage 6 on s: the
+// neighbourhoods, the connect checks and their pair checks.
+template <class ZT>
+GBP_INTERNAL int star_enqueue_checks(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, int32_t half,
+                                     int direction, int adaptive, gbp_plan_ws::TimedHalf *th,
+                                     hipStream_t s);
+// stage 7 on star_stream behind what s holds: the ordered replay into T
+// (tree kT: Ta 0, Tb 1)
+GBP_INTERNAL int star_enqueue_replay(gbp_plan_ws *w, gbp_tree *T, int32_t half, int kT,
+                                     gbp_plan_ws::TimedHalf *th, hipStream_t s);
+// after Tb's half, on star_stream behind s's stage 5: the kept connections
+// ranked with the trees' current g (ga: Ta's, gb: Tb's)
+GBP_INTERNAL int star_enqueue_rank(gbp_plan_ws *w, int32_t half, int kT, const double *ga,
+                                   const double *gb, hipStream_t s);
+// the workspace's side stream and its events released (gbp_plan.hip's ws_free)
+GBP_INTERNAL void star_stream_destroy(gbp_plan_ws *w);
 
 // the persistent validate kernel with the batch size read on the device from
 // n_dev (n_max bounds the grid); gbp_engine.hip

@@ -706,7 +706,7 @@ typedef struct {
   uint32_t commit_fin;    /* reserved (unused since the look-ahead search) */
   int64_t ext_prev, stat_targets_prev;
   /* reserved (unused): gbp_plan_halves_dev's drawn-ahead targets are
-   * counted in the workspace's look-ahead state (gbp_plan.hip gbp_plan_la) */
+   * counted in the workspace's look-ahead state (gbp_internal.h gbp_plan_la) */
   int32_t pre_targets, pre_fragile;
   /* RRT*-Connect (gbp_plan_star_config): the last half's neighbour pairs
    * (new vertex, vertex before it within delta) and their connect checks

@@ -39,6 +39,16 @@ def test_exports_are_plain_c():
     assert "gbp_" not in "".join(l for l in out.splitlines() if "_Z" in l and "gbp" in l)
 
 
+def test_makefile_links_every_unit():
+    """Every csrc/*.hip is in the Makefile's SRC: a unit left out of the link
+    would show up only as a missing symbol where the library is loaded."""
+    csrc = os.path.join(ROOT, "global_body_planner_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read().replace("\\\n", " ")
+    src = re.search(r"^SRC\s*:=\s*(.*)$", mk, flags=re.M).group(1).split()
+    units = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert len(units) >= 9 and sorted(src) == units
+
+
 def test_load_version_and_status_strings():
     lib = L.load()
     assert lib.gbp_version() == 200

@@ -1,5 +1,6 @@
 """The search resident on the device (include/gbp.h "device trees and the
-device planner loop"; csrc/gbp_plan.hip) against the host-driven batched
+device planner loop"; csrc/gbp_plan.hip, its searches csrc/gbp_nn.hip, the
+trees csrc/gbp_tree.hip) against the host-driven batched
 planner it replaces (csrc/host/gbp_planner.cpp buildRRTConnectBatched), and
 the device tree / extend-into-tree primitives (SURVEY §8(b) items 4-5,
 §8(f) row 1) against the engine's batched primitives and the oracle.

@@ -9,7 +9,7 @@ on synth-rough-1024 at SURVEY §8(d)'s 43,690 targets per half-iteration
 machinery that small batches never reach is active:
 
   * the next half's targets drawn inside the current half's matrix-core search
-    launch and committed by its last append (gbp_plan.hip NhDraw, commit_pre);
+    launch and committed by its last append (gbp_nn.h NhDraw, commit_pre);
   * the ordered look-back over ~360 tiles of draws and ~170 of targets;
   * trees of tens of thousands of vertices, so the MFMA nearest-vertex search
     re-checks units in fp64 and runs whole-segment scans (nn_scans > 0) on the

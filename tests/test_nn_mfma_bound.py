@@ -1,5 +1,5 @@
 """The matrix-core nearest-neighbour search's threshold (global_body_planner_amd/
-csrc/gbp_plan.hip: k_nn_mfma, nn_put_hrow, nh_eps, nh_threshold) restated in
+csrc/gbp_nn.hip: k_nn_mfma, nh_eps, nh_threshold; gbp_hrow.h: nn_put_hrow) restated in
 numpy and checked on the CPU: the scores S~_j = |F_j|^2 - 2 G.F_j are formed as
 the two v_mfma_f32_32x32x16_f16 do (F = 64 v and G = 64 q split into fp16
 hi + lo, the squared norm times 2^-14 in three fp16 parts against the query
