@@ -167,8 +167,8 @@ __global__ __launch_bounds__(256, W) void k_validate_direct(
   Acc acc{0, 0, 0};
   uint32_t f = 0;
   const int d = dir ? dir[i] : dir_all;
-  const bool v = (d == GBP_FORWARD) ? pair_forward<ZT, ADAPTIVE>(T, s, a, sn, tn, acc, f)
-                                    : pair_reverse<ZT, ADAPTIVE>(T, s, a, sn, tn, acc, f);
+  const bool v = (d == GBP_FORWARD) ? pair_forward<ADAPTIVE>(T, s, a, sn, tn, acc, f)
+                                    : pair_reverse<ADAPTIVE>(T, s, a, sn, tn, acc, f);
   f |= acc.flags | (v ? GBP_F_VALID : 0u);
   if (valid) valid[i] = v;
   if (s_new && (f & GBP_F_SNEW_SET)) {

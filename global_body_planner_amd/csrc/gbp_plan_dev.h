@@ -6,6 +6,7 @@
 
 #include <type_traits>
 
+#include "gbp_closed_forms.h"
 #include "gbp_internal.h"
 #include "gbp_lane.h"
 
@@ -39,25 +40,7 @@ __device__ __forceinline__ void raise_gate(gbp_plan_status *st, uint64_t seq) {
 #define GBP_SHORTCUT_GC 4  // k_shortcut_pairs workgroups (4 waves, one pair each) per CU
 #endif
 
-// rrt_connect.cpp:53-63
-__device__ __forceinline__ void connect_action(const double *s_start, const double *s_goal,
-                                               double t_s, double *a) {
-  const double x_td = s_start[0], y_td = s_start[1], z_td = s_start[2];
-  const double dx_td = s_start[3], dy_td = s_start[4], dz_td = s_start[5];
-  const double x_to = s_goal[0], y_to = s_goal[1], z_to = s_goal[2];
-  const double dx_to = s_goal[3], dy_to = s_goal[4], dz_to = s_goal[5];
-  const double p_td = s_start[6], dp_td = s_start[7], p_to = s_goal[6], dp_to = s_goal[7];
-  a[0] = -(2.0 * (3.0 * x_td - 3.0 * x_to + 2.0 * dx_td * t_s + dx_to * t_s)) / (t_s * t_s);
-  a[1] = -(2.0 * (3.0 * y_td - 3.0 * y_to + 2.0 * dy_td * t_s + dy_to * t_s)) / (t_s * t_s);
-  a[2] = -(2.0 * (3.0 * z_td - 3.0 * z_to + 2.0 * dz_td * t_s + dz_to * t_s)) / (t_s * t_s);
-  a[3] = (2.0 * (3.0 * x_td - 3.0 * x_to + dx_td * t_s + 2.0 * dx_to * t_s)) / (t_s * t_s);
-  a[4] = (2.0 * (3.0 * y_td - 3.0 * y_to + dy_td * t_s + 2.0 * dy_to * t_s)) / (t_s * t_s);
-  a[5] = (2.0 * (3.0 * z_td - 3.0 * z_to + dz_td * t_s + 2.0 * dz_to * t_s)) / (t_s * t_s);
-  a[6] = t_s;
-  a[7] = 0;
-  a[8] = -(2.0 * (3.0 * p_td - 3.0 * p_to + 2.0 * dp_td * t_s + dp_to * t_s)) / (t_s * t_s);
-  a[9] = (2.0 * (3.0 * p_td - 3.0 * p_to + dp_td * t_s + 2.0 * dp_to * t_s)) / (t_s * t_s);
-}
+// connect_action (rrt_connect.cpp:53-63): gbp_closed_forms.h
 
 // One pair check (planning_utils.cpp:645-881) by a whole wave: every lane
 // holds the same Lane state (wave-uniform); per step, lane j evaluates the

@@ -8,6 +8,7 @@
 #include "gbp_planner.h"
 #include "gbp_tree_path.h"
 #include "gbp_tree_prune.h"
+#include "../gbp_closed_forms.h"
 #include "../gbp_um_order.h"
 
 #include <algorithm>
@@ -878,27 +879,6 @@ static void tree_extent(const std::vector<State> &vertices, double e[4]) {
   }
 }
 
-static Action connect_action(const State &s_start, const State &s_goal, double t_s) {
-  // rrt_connect.cpp:53-63 (cubic-Hermite stance action, t_f = 0)
-  const double x_td = s_start[0], y_td = s_start[1], z_td = s_start[2];
-  const double dx_td = s_start[3], dy_td = s_start[4], dz_td = s_start[5];
-  const double x_to = s_goal[0], y_to = s_goal[1], z_to = s_goal[2];
-  const double dx_to = s_goal[3], dy_to = s_goal[4], dz_to = s_goal[5];
-  const double p_td = s_start[6], dp_td = s_start[7], p_to = s_goal[6], dp_to = s_goal[7];
-  Action a;
-  a[0] = -(2.0 * (3.0 * x_td - 3.0 * x_to + 2.0 * dx_td * t_s + dx_to * t_s)) / (t_s * t_s);
-  a[1] = -(2.0 * (3.0 * y_td - 3.0 * y_to + 2.0 * dy_td * t_s + dy_to * t_s)) / (t_s * t_s);
-  a[2] = -(2.0 * (3.0 * z_td - 3.0 * z_to + 2.0 * dz_td * t_s + dz_to * t_s)) / (t_s * t_s);
-  a[3] = (2.0 * (3.0 * x_td - 3.0 * x_to + dx_td * t_s + 2.0 * dx_to * t_s)) / (t_s * t_s);
-  a[4] = (2.0 * (3.0 * y_td - 3.0 * y_to + dy_td * t_s + 2.0 * dy_to * t_s)) / (t_s * t_s);
-  a[5] = (2.0 * (3.0 * z_td - 3.0 * z_to + dz_td * t_s + 2.0 * dz_to * t_s)) / (t_s * t_s);
-  a[6] = t_s;
-  a[7] = 0;
-  a[8] = -(2.0 * (3.0 * p_td - 3.0 * p_to + 2.0 * dp_td * t_s + dp_to * t_s)) / (t_s * t_s);
-  a[9] = (2.0 * (3.0 * p_td - 3.0 * p_to + dp_td * t_s + 2.0 * dp_to * t_s)) / (t_s * t_s);
-  return a;
-}
-
 int RRTConnectClass::attemptConnect(State s_existing, State s, double t_s, State &s_new,
                                     Action &a_new, FastTerrainMap &terrain, int direction) {
   std::vector<int> r;
@@ -948,7 +928,8 @@ void RRTConnectClass::attemptConnectBatch(const std::vector<State> &s_existing,
       if (t_s[k] <= KINEMATICS_RES) continue;  // TRAPPED (:23-24)
       const State &start = (direction == FORWARD) ? s_existing[k] : s[k];
       const State &goal = (direction == FORWARD) ? s[k] : s_existing[k];
-      const Action a = connect_action(start, goal, t_s[k]);
+      Action a;  // rrt_connect.cpp:53-63 (cubic-Hermite stance action, t_f = 0)
+      gbp::connect_action(start.data(), goal.data(), t_s[k], a.data());
       a_new[k] = a;
       if (!isValidAction(a)) continue;  // TRAPPED (:66, :83)
       chk_idx.push_back(k);

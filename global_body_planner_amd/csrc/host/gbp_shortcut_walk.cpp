@@ -8,6 +8,7 @@
 #include <array>
 #include <cmath>
 
+#include "../gbp_closed_forms.h"
 #include "gbp_host_check.h"
 
 namespace gbp_shortcut {
@@ -16,21 +17,12 @@ namespace {
 using State = std::array<double, 8>;
 using Action = std::array<double, 10>;
 
-constexpr double V_NOM = 0.75;     // planning_utils.h:28
-constexpr double MY_PI = 3.14159;  // planning_utils.h:15
-
-inline double std_min(double a, double b) { return (b < a) ? b : a; }
-inline double std_max(double a, double b) { return (a < b) ? b : a; }
+using gbp::V_NOM;
 
 double state_yaw_distance(const State &q1, const State &q2) {  // planning_utils.h:133-145
   const double yaw1 = std::atan2(q1[4], q1[3]);
   const double yaw2 = std::atan2(q2[4], q2[3]);
-  const double yaw_min = std_min(yaw1, yaw2), yaw_max = std_max(yaw1, yaw2);
-  return std_min(yaw_max - yaw_min, yaw_min + 2 * MY_PI - yaw_max);
-}
-
-inline double weighted_cost(const CostWeights &cw, double length, double yaw) {
-  return cw.add_yaw ? length * cw.length_weight + yaw * cw.yaw_weight : length;
+  return gbp::yaw_distance(yaw1, yaw2);
 }
 
 }  // namespace
@@ -60,6 +52,9 @@ int64_t walk(int64_t n, const double *states, const double *actions, const uint8
   int64_t at = 0;  // s's place in the path: the table's row, nothing else
   keep(s, nullptr);
   double len = 0, yaw = 0, cost = 0;
+  auto weighted_cost = [&](double dl, double dy) {
+    return gbp::weighted_cost(cw.add_yaw != 0, cw.length_weight, cw.yaw_weight, dl, dy);
+  };
   while (s != s_goal) {
     // the reference copies both sequences and pops their backs; `back` is the
     // place of the state copy's back(), whose action is the action copy's
@@ -94,7 +89,7 @@ int64_t walk(int64_t n, const double *states, const double *actions, const uint8
       const double dy = state_yaw_distance(s, s_next);
       len += dl;
       yaw += dy;
-      cost += weighted_cost(cw, dl, dy);
+      cost += weighted_cost(dl, dy);
       s = s_next;
       at = back;
     } else {
@@ -102,7 +97,7 @@ int64_t walk(int64_t n, const double *states, const double *actions, const uint8
       keep(old_state, &old_action);
       const double dl = gbp_host::pose_distance(s.data(), old_state.data());
       const double dy = state_yaw_distance(s, old_state);
-      cost += weighted_cost(cw, dl, dy);
+      cost += weighted_cost(dl, dy);
       s = old_state;
       at = old_at;
     }

@@ -29,43 +29,44 @@
 namespace gbp_amd {
 
 namespace planning_utils {
-// include/global_body_planner/planning_utils.h:21-66
-const double H_MAX = 0.4;
-const double H_MIN = 0.075;
-const double V_MAX = 2.0;
-const double V_NOM = 0.75;
-const double P_MAX = 1.0;
-const double DP_MAX = 3.0;
-const double ANG_ACC_MAX = 7.0;
-const double ROBOT_L = 0.3;
-const double ROBOT_W = 0.3;
-const double ROBOT_H = 0.05;
-const double M_CONST = 13;
-const double G_CONST = 9.81;
-const double F_MAX = 637;
-const double MU = 1.0;
-const double T_S_MIN = 0.3;
-const double T_S_MAX = 0.3;
-const double T_F_MIN = 0.0;
-const double T_F_MAX = 0.5;
-const double KINEMATICS_RES = 0.05;
-const double BACKUP_TIME = 0.2;
-const double BACKUP_RATIO = 0.5;
-const int NUM_GEN_STATES = 6;
-const double GOAL_BOUNDS = 0.5;
-const int FLIGHT = 0;
-const int STANCE = 1;
-const int CONNECT_STANCE = 2;
-const int FORWARD = 0;
-const int REVERSE = 1;
-const int POSEDIM = 3;
-const int STATEDIM = 8;
-const int ACTIONDIM = 10;
+// include/global_body_planner/planning_utils.h:21-66 (constexpr: csrc/host/
+// gbp_planning_math.cpp asserts each equal to the engine's own statement)
+constexpr double H_MAX = 0.4;
+constexpr double H_MIN = 0.075;
+constexpr double V_MAX = 2.0;
+constexpr double V_NOM = 0.75;
+constexpr double P_MAX = 1.0;
+constexpr double DP_MAX = 3.0;
+constexpr double ANG_ACC_MAX = 7.0;
+constexpr double ROBOT_L = 0.3;
+constexpr double ROBOT_W = 0.3;
+constexpr double ROBOT_H = 0.05;
+constexpr double M_CONST = 13;
+constexpr double G_CONST = 9.81;
+constexpr double F_MAX = 637;
+constexpr double MU = 1.0;
+constexpr double T_S_MIN = 0.3;
+constexpr double T_S_MAX = 0.3;
+constexpr double T_F_MIN = 0.0;
+constexpr double T_F_MAX = 0.5;
+constexpr double KINEMATICS_RES = 0.05;
+constexpr double BACKUP_TIME = 0.2;
+constexpr double BACKUP_RATIO = 0.5;
+constexpr int NUM_GEN_STATES = 6;
+constexpr double GOAL_BOUNDS = 0.5;
+constexpr int FLIGHT = 0;
+constexpr int STANCE = 1;
+constexpr int CONNECT_STANCE = 2;
+constexpr int FORWARD = 0;
+constexpr int REVERSE = 1;
+constexpr int POSEDIM = 3;
+constexpr int STATEDIM = 8;
+constexpr int ACTIONDIM = 10;
 typedef std::array<double, STATEDIM> State;
 typedef std::array<double, ACTIONDIM> Action;
 typedef std::pair<State, Action> StateActionPair;
-const double INFTY = 1.7976931348623157e308;
-const double MY_PI = 3.14159;
+constexpr double INFTY = 1.7976931348623157e308;
+constexpr double MY_PI = 3.14159;
 }  // namespace planning_utils
 
 using planning_utils::Action;
