@@ -21,6 +21,7 @@ F_VALID, F_OOD, F_NAN, F_SNEW_SET, F_TNEW_SET, F_FRAGILE, F_LIMIT, F_RESOLVED = 
 MAX_SAMPLES = 7000
 F_STAGE_SHIFT = 8
 F_STAGE_MASK = 0xF << F_STAGE_SHIFT
+F_GRAFT_CANDIDATE, F_GRAFT_CHECKED = 1 << 16, 1 << 17
 STORAGE_AUTO, STORAGE_F32, STORAGE_F64 = 0, 1, 2
 OPT_KERNEL, OPT_BLOCK, OPT_WAVES, OPT_LDS_COORDS, OPT_HELPERS = 1, 2, 4, 5, 8
 OPT_AFFINE_COORDS, OPT_COORD_MODE, OPT_XCD_MAP, OPT_FAST_RCP, OPT_FRAGILE_EPS = 9, 10, 13, 14, 15
@@ -69,6 +70,8 @@ EXPORTS = [
     "gbp_plan_shared_read_host", "gbp_plan_shared_load_host", "gbp_plan_shared_remap_dev",
     "gbp_tree_path_dev", "gbp_tree_path_host",
     "gbp_tree_revalidate_keep_host", "gbp_tree_reroot_keep_host",
+    "gbp_tree_graft_check_dev", "gbp_tree_graft_dev", "gbp_tree_graft_last",
+    "gbp_tree_graft_host", "gbp_tree_graft_keep_host",
 ]
 
 
@@ -97,6 +100,15 @@ class RerootStats(ctypes.Structure):
     _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
                 ("n_outside", ctypes.c_int64), ("n_edge_invalid", ctypes.c_int64),
                 ("n_inherited", ctypes.c_int64), ("depth", ctypes.c_int64)]
+
+
+class GraftStats(ctypes.Structure):
+    """gbp_graft_stats (include/gbp.h): what a graft checked, attached and kept."""
+    _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
+                ("n_candidates", ctypes.c_int64), ("n_checked", ctypes.c_int64),
+                ("n_attached", ctypes.c_int64), ("n_outside", ctypes.c_int64),
+                ("n_edge_invalid", ctypes.c_int64), ("n_inherited", ctypes.c_int64),
+                ("depth", ctypes.c_int64)]
 
 
 class SharedStats(ctypes.Structure):
@@ -209,6 +221,11 @@ def load(path=None):
         "gbp_tree_reroot_last": (I, [P, P]),
         "gbp_tree_revalidate_keep_host": (I, [P, P, I, I, P, P, I64, P, P]),
         "gbp_tree_reroot_keep_host": (I, [P, P, ctypes.c_int32, I, I, P, P, I64, P, P]),
+        "gbp_tree_graft_check_dev": (I, [P, P, I64, P, ctypes.c_double, I, I, P, P, P, P]),
+        "gbp_tree_graft_dev": (I, [P, I64, P, P, P, P, P, P, P]),
+        "gbp_tree_graft_last": (I, [P, P]),
+        "gbp_tree_graft_host": (I, [P, P, P, ctypes.c_double, I, I, I, P, P, P]),
+        "gbp_tree_graft_keep_host": (I, [P, P, P, ctypes.c_double, I, I, I, P, P, I64, P, P]),
         "gbp_plan_ws_create": (I, [P, I64, P]),
         "gbp_plan_ws_destroy": (I, [P]),
         "gbp_plan_reset": (I, [P, I64, P]),

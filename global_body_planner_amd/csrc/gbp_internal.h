@@ -4,8 +4,9 @@
 // workspace; gbp_nn.hip: the nearest-neighbour search in a device tree;
 // gbp_star.hip: RRT*'s insertion; gbp_shortcut.hip: the connect table of
 // found paths; gbp_tree.hip: the device tree handle;
-// gbp_tree_maint.hip: a device tree pruned against a changed terrain or
-// re-rooted at one of its vertices;
+// gbp_tree_maint.hip: a device tree pruned against a changed terrain,
+// re-rooted at one of its vertices or grafted onto a root state that is none
+// of them; gbp_tree_graft.hip: the graft's connect checks;
 // gbp_terrain.hip: a handle's heights updated in place and its host mirror;
 // gbp_replan.hip: RRT*'s kept connections carried between searches and the
 // joined path of two device trees): the handles, the block sizes, the device

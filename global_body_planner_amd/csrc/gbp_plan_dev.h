@@ -1,5 +1,6 @@
 // gbp_plan_dev.h — what the planner's translation units share on the device
-// (gbp_plan.hip, gbp_nn.hip, gbp_star.hip, gbp_shortcut.hip): the launch gate,
+// (gbp_plan.hip, gbp_nn.hip, gbp_star.hip, gbp_shortcut.hip) and the graft's
+// checks (gbp_tree_graft.hip): the launch gate,
 // the connect action and the pair check by a whole wave, and the host's pick
 // of their <ADAPTIVE, CM> instantiation.  Device only; not part of the C ABI.
 #pragma once
@@ -28,7 +29,7 @@ __device__ __forceinline__ void raise_gate(gbp_plan_status *st, uint64_t seq) {
 
 // ============================================================================
 // RRTConnectClass::attemptConnect (rrt_connect.cpp:20-91): what stage 4's
-// k_connect, RRT*'s k_star_check and k_shortcut_pairs share
+// k_connect, RRT*'s k_star_check, k_shortcut_pairs and k_graft_check share
 // ============================================================================
 #ifndef GBP_STAR_GC
 #define GBP_STAR_GC 2  // k_star_check workgroups (4 waves) per CU

@@ -3,7 +3,7 @@
 // read, read_links, append_host, load_host, device_ptrs, and the planner
 // streams.  The handle and its allocations' list: gbp_internal.h; the fp16
 // rows' writer: gbp_hrow.h; the planner's appends: gbp_plan.hip (k_append);
-// a tree pruned or re-rooted: gbp_tree_maint.hip.
+// a tree pruned, re-rooted or grafted: gbp_tree_maint.hip.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>

@@ -2,7 +2,9 @@
 // changed terrain (gbp_tree_revalidate_dev, gbp_tree_prune_dev,
 // gbp_tree_revalidate_host / _keep_host) or re-rooted at one of
 // its vertices (gbp_tree_reroot_dev, gbp_tree_reroot_host / _keep_host,
-// gbp_tree_reroot_last).  A translation unit of its own beside
+// gbp_tree_reroot_last) or grafted onto a root state that is none
+// of them (gbp_tree_graft_dev, gbp_tree_graft_host / _keep_host; DESIGN §5.11;
+// its stage A is gbp_tree_graft.hip's).  A translation unit of its own beside
 // gbp_replan.hip: the planner loop (gbp_plan.hip) does not depend on it.
 //
 // Both are one pipeline (tree_keep) around a new root k, the prune with k = 0:
@@ -13,7 +15,9 @@
 // k_prune_move_links move them into fresh arrays.  The re-root (DEPTH) sums the
 // depth below k along the jumps and derives g again level by level
 // (k_reroot_levels / k_reroot_order sort the vertices by depth,
-// k_reroot_g_wide / k_reroot_g_narrow write g).
+// k_reroot_g_wide / k_reroot_g_narrow write g).  The graft (GRAFT) is the
+// re-root at one more vertex, the root state, under which the attached
+// vertices hang (k_graft_attach, k_graft_root).
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -86,20 +90,30 @@ __global__ __launch_bounds__(TB) void k_prune_gather(gbp_tree t, int32_t n, doub
 // far (terminals add 0): integer sums are associative, so the depth below k
 // is exact.  edge_valid may be null (every edge holds); edge_valid[k] is never
 // read.
-template <bool DEPTH>
+//
+// GRAFT (the graft): the tree of n vertices whose last one, k =
+// n - 1, is the new root state and has no row in parent / edge_valid /
+// attach; an attached vertex's parent is k and its own old edge is ignored,
+// the old root included.  Everything else is the re-root at k.
+template <bool DEPTH, bool GRAFT = false>
 __global__ __launch_bounds__(TB) void k_keep_seed(const int32_t *__restrict__ parent,
-                                                  const uint8_t *__restrict__ edge_valid, int32_t n,
+                                                  const uint8_t *__restrict__ edge_valid,
+                                                  const uint8_t *__restrict__ attach, int32_t n,
                                                   int32_t k, uint32_t *__restrict__ w,
                                                   uint32_t *__restrict__ d) {
+  const int32_t nv = GRAFT ? k : n;  // the vertices parent[] may name
   for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
     uint32_t x, e = 0;
     if (i == k) {
       x = (uint32_t)k << 1;
+    } else if (GRAFT && attach[i]) {
+      x = (uint32_t)k << 1;
+      e = 1u;
     } else if (i == 0) {
       x = 1u;
     } else {
       const int32_t p = parent[i];
-      const bool in = p >= 0 && p < n;
+      const bool in = p >= 0 && p < nv;
       x = in ? ((uint32_t)p << 1) | ((edge_valid && !edge_valid[i]) ? 1u : 0u) : 1u;
       e = in ? 1u : 0u;
     }
@@ -142,17 +156,18 @@ using KeepTile = TileRec<DEPTH ? 4 : 2>;
 template <bool DEPTH>
 using KeepStats = std::conditional_t<DEPTH, gbp_reroot_stats, gbp_prune_stats>;
 
-template <bool DEPTH>
+template <bool DEPTH, bool GRAFT = false>
 __global__ __launch_bounds__(CB) void k_keep_count(const uint32_t *__restrict__ w,
                                                    const uint32_t *__restrict__ d,
-                                                   const uint8_t *__restrict__ edge_valid, int32_t n,
+                                                   const uint8_t *__restrict__ edge_valid,
+                                                   const uint8_t *__restrict__ attach, int32_t n,
                                                    int32_t k, KeepTile<DEPTH> *__restrict__ tile) {
   const int64_t i = (int64_t)blockIdx.x * CB + threadIdx.x;
   const bool in = i < n;
   const uint32_t x = in ? w[i] : 1u;
   const bool below = in && keep_below<DEPTH>(x, k);
   const bool keep = below && !(x & 1u);
-  const bool bad = below && i != k && edge_valid && !edge_valid[i];
+  const bool bad = below && i != k && !(GRAFT && attach[i]) && edge_valid && !edge_valid[i];
   KeepTile<DEPTH> t;
   if constexpr (DEPTH)
     t = tile_count<4, true>({keep && i != k, bad, in && !below}, keep ? d[i] : 0u);
@@ -189,8 +204,8 @@ __global__ __launch_bounds__(CB) void k_keep_scan(const KeepTile<DEPTH> *__restr
 // remap (k -> 0, the other kept vertices from 1 in their order); with DEPTH
 // every kept vertex's depth under its new index and the levels' sizes (hist
 // zeroed before this launch; an integer count does not depend on the atomics'
-// order)
-template <bool DEPTH>
+// order).  GRAFT: k has no entry in remap.
+template <bool DEPTH, bool GRAFT = false>
 __global__ __launch_bounds__(CB) void k_keep_rank(const uint32_t *__restrict__ w,
                                                   const uint32_t *__restrict__ d, int32_t n, int32_t k,
                                                   const uint32_t *__restrict__ toff,
@@ -203,7 +218,7 @@ __global__ __launch_bounds__(CB) void k_keep_rank(const uint32_t *__restrict__ w
   const uint32_t at = tile_rank(keep && i != k, toff[blockIdx.x]);
   if (i >= n) return;
   const int32_t j = !keep ? -1 : i == k ? 0 : (int32_t)at;
-  remap[i] = j;
+  if (!GRAFT || i != k) remap[i] = j;
   if constexpr (DEPTH) {
     if (j >= 0) {
       depth[j] = d[i];
@@ -232,11 +247,14 @@ __global__ __launch_bounds__(TB) void k_prune_move_rows(gbp_tree o, gbp_tree f, 
 
 // the next kept vertex of a successor list from c on (c itself included),
 // renumbered; -1 at the list's end.  A list holds at most n vertices: the walk
-// stops there whatever the arrays hold.
+// stops there whatever the arrays hold.  GRAFT: an attached vertex has left
+// its old parent's list, kept though it is.
+template <bool GRAFT>
 __device__ __forceinline__ int32_t prune_next_kept(int32_t c, const int32_t *__restrict__ link,
-                                                   const int32_t *__restrict__ remap, int32_t n) {
+                                                   const int32_t *__restrict__ remap,
+                                                   const uint8_t *__restrict__ attach, int32_t n) {
   for (int32_t steps = 0; c >= 0 && c < n && steps < n; c = link[c], steps++)
-    if (remap[c] >= 0) return remap[c];
+    if (remap[c] >= 0 && !(GRAFT && attach[c])) return remap[c];
   return -1;
 }
 
@@ -245,9 +263,12 @@ __device__ __forceinline__ int32_t prune_next_kept(int32_t c, const int32_t *__r
 // places in the successor lists: the old lists with the pruned vertices left
 // out, so each list keeps its order.  Every word written belongs to the
 // vertex's own fresh row.  A new root's old parent is not kept, so its parent
-// becomes -1 and it is in no list.
+// becomes -1 and it is in no list.  GRAFT: n is the old tree's size; an
+// attached vertex's parent and places in the root's list are k_graft_root's.
+template <bool GRAFT = false>
 __global__ __launch_bounds__(TB) void k_prune_move_links(gbp_tree o, gbp_tree f, int32_t n,
-                                                         const int32_t *__restrict__ remap) {
+                                                         const int32_t *__restrict__ remap,
+                                                         const uint8_t *__restrict__ attach) {
   for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
     const int32_t j = remap[i];
     if (j < 0) continue;
@@ -257,9 +278,9 @@ __global__ __launch_bounds__(TB) void k_prune_move_links(gbp_tree o, gbp_tree f,
     double s[8];
     copy8(s, o.v + 8 * i);
     nn_put_hrow(f.vh, f.hm, j, s, false);
-    f.child[j] = prune_next_kept(o.child[i], o.sibling, remap, n);
-    f.sibling[j] = prune_next_kept(o.sibling[i], o.sibling, remap, n);
-    f.prev[j] = prune_next_kept(o.prev[i], o.prev, remap, n);
+    f.child[j] = prune_next_kept<GRAFT>(o.child[i], o.sibling, remap, attach, n);
+    f.sibling[j] = prune_next_kept<GRAFT>(o.sibling[i], o.sibling, remap, attach, n);
+    f.prev[j] = prune_next_kept<GRAFT>(o.prev[i], o.prev, remap, attach, n);
   }
 }
 
@@ -321,6 +342,81 @@ __global__ __launch_bounds__(TB) void k_reroot_g_narrow(gbp_tree t, const int32_
 }
 
 // ============================================================================
+// the graft's own part: the attached vertices under the new root
+// ============================================================================
+// after the move: an attached vertex hangs under the new root, vertex 0, by its
+// connect action (every attached vertex is kept)
+__global__ __launch_bounds__(TB) void k_graft_attach(gbp_tree f, int32_t n,
+                                                     const int32_t *__restrict__ remap,
+                                                     const uint8_t *__restrict__ attach,
+                                                     const double *__restrict__ actions) {
+  for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < n; i += (int64_t)gridDim.x * TB) {
+    if (!attach[i]) continue;
+    const int64_t j = remap[i];
+    if (j < 0) continue;
+    f.parent[j] = 0;
+    copy10(f.a + 10 * j, actions + 10 * i);
+  }
+}
+
+struct GraftState {  // the root state travels as the kernel's argument
+  double s[8];
+};
+
+// one workgroup, after k_graft_attach: the new root's row (its action is
+// k_reroot_levels'), its successor list (the vertices whose parent is 0, the
+// attached ones and no others, in ascending index: att[] lists them, then
+// each links to its neighbours) and the call's record from the keep's
+__global__ __launch_bounds__(CB) void k_graft_root(gbp_tree f, GraftState R, int32_t *__restrict__ att,
+                                                   const gbp_reroot_stats *__restrict__ rs,
+                                                   gbp_graft_stats *__restrict__ gs) {
+  __shared__ uint32_t sw[CB / WAVE];
+  const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+  const int64_t m = *f.count;
+  if (threadIdx.x == 0) {
+    copy8(f.v, R.s);
+    nn_put_hrow(f.vh, f.hm, 0, R.s, false);
+    f.parent[0] = -1;
+    f.g[0] = 0.0;
+    f.sibling[0] = -1;
+    f.prev[0] = -1;
+  }
+  uint32_t total = 0;  // the same in every thread
+  for (int64_t base = 0; base < m; base += CB) {
+    const int64_t j = base + threadIdx.x;
+    const bool is = j >= 1 && j < m && f.parent[j] == 0;
+    const unsigned long long bm = __ballot(is);
+    if (lane == 0) sw[wv] = (uint32_t)__popcll(bm);
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (int q = 0; q < CB / WAVE; q++) {
+      if (q < wv) before += sw[q];
+      all += sw[q];
+    }
+    if (is) att[total + before + (uint32_t)__popcll(bm & ((1ull << lane) - 1ull))] = (int32_t)j;
+    total += all;
+    __syncthreads();  // sw is read before the next pass writes it; att before the links read it
+  }
+  for (uint32_t x = threadIdx.x; x < total; x += CB) {
+    const int32_t j = att[x];
+    f.sibling[j] = x + 1 < total ? att[x + 1] : -1;
+    f.prev[j] = x > 0 ? att[x - 1] : -1;
+  }
+  if (threadIdx.x == 0) {
+    f.child[0] = total ? att[0] : -1;
+    gs->n_before = rs->n_before - 1;  // (the keep counted the root state's vertex)
+    gs->n_kept = rs->n_kept;
+    gs->n_candidates = 0;
+    gs->n_checked = 0;
+    gs->n_attached = total;
+    gs->n_outside = rs->n_outside;
+    gs->n_edge_invalid = rs->n_edge_invalid;
+    gs->n_inherited = rs->n_inherited;
+    gs->depth = rs->depth;
+  }
+}
+
+// ============================================================================
 // host side
 // ============================================================================
 // stage A's attempt rows in the tree's own grow-only buffer (the call only
@@ -338,9 +434,12 @@ int prune_args(const gbp_tree *tree, int64_t n, bool arrays) {
 
 // What a re-root adds to tree_keep (RerootDepth below); the prune adds nothing.
 struct NoDepth {
-  static constexpr bool DEPTH = false;
+  static constexpr bool DEPTH = false, GRAFT = false;
+  using Stats = gbp_prune_stats;
+  const uint8_t *attach = nullptr;
   uint32_t *d[2] = {nullptr, nullptr}, *depth = nullptr, *hist = nullptr;
   void carve(Stage &, int64_t) {}
+  gbp_prune_stats *keep_stats(gbp_prune_stats *s) { return s; }
   void mark(int, hipStream_t) {}
   bool before_rank(int64_t, hipStream_t) { return true; }
   int after_move(const gbp_tree &, int64_t, unsigned, const gbp_prune_stats *, hipStream_t) {
@@ -353,28 +452,36 @@ struct NoDepth {
 // stats written on the device.  The survivors get arrays, a count and search
 // bounds of their own: until the swap at the end the tree is untouched, so a
 // failed call leaves it as it was.  Synchronises the stream.
+// The graft (Extra::GRAFT, GraftRoot below) runs the rule on nv = n + 1
+// vertices, the last one the new root state k = n, which has no row in the
+// tree: the moves take the n old rows, and the fresh arrays hold nv rows at
+// least.
 template <class Extra>
 int tree_keep(gbp_tree *tree, int64_t n, int32_t k, const uint8_t *edge_valid, int32_t *remap,
-              KeepStats<Extra::DEPTH> *stats, hipStream_t s, Extra &x) {
-  constexpr bool DEPTH = Extra::DEPTH;
+              typename Extra::Stats *stats, hipStream_t s, Extra &x) {
+  constexpr bool DEPTH = Extra::DEPTH, GRAFT = Extra::GRAFT;
   int rc = prune_args(tree, n, remap && stats && (DEPTH || edge_valid));
   if (rc) return rc;
   int64_t have = 0;
   if ((rc = gbp_tree_size(tree, &have, s))) return rc;  // synchronises
   if (have != n) return GBP_E_SHAPE;
-  if (k < 0 || k >= n) return GBP_E_INVALID_ARG;
+  const int64_t nv = n + (GRAFT ? 1 : 0);
+  if (GRAFT) k = (int32_t)n;
+  if (k < 0 || k >= nv || nv > 0x7FFFFFFF) return GBP_E_INVALID_ARG;
   DeviceGuard g(tree->device);
-  const int64_t ntile = (n + CB - 1) / CB;
+  const int64_t ntile = (nv + CB - 1) / CB;
   DevBuf buf;
   uint32_t *w[2], *toff;
   KeepTile<DEPTH> *tile;
   rc = stage_buf(buf, [&](Stage &S) {
-    S.take(w[0], n); S.take(w[1], n); S.take(tile, ntile); S.take(toff, ntile);
-    x.carve(S, n);
+    S.take(w[0], nv); S.take(w[1], nv); S.take(tile, ntile); S.take(toff, ntile);
+    x.carve(S, nv);
   });
   if (rc) return rc;
+  KeepStats<DEPTH> *kst = x.keep_stats(stats);
   gbp_tree fresh = *tree;
-  if ((rc = tree_alloc(&fresh, tree->cap))) return rc;
+  const int64_t cap = nv > tree->cap ? std::min<int64_t>(std::max(2 * tree->cap, nv), 0x7FFFFFFF) : tree->cap;
+  if ((rc = tree_alloc(&fresh, cap))) return rc;
   fresh.count = nullptr;
   fresh.hm = nullptr;
   auto drop_fresh = [&](int code) {
@@ -386,29 +493,30 @@ int tree_keep(gbp_tree *tree, int64_t n, int32_t k, const uint8_t *edge_valid, i
   };
   if (hipMalloc(&fresh.count, 4) != hipSuccess || hipMalloc(&fresh.hm, 64) != hipSuccess)
     return drop_fresh(GBP_E_ALLOC);
-  const unsigned gv = grid_for(n, TB, 2048);
+  const unsigned gv = grid_for(nv, TB, 2048);
   x.mark(0, s);
-  hipLaunchKernelGGL(k_keep_seed<DEPTH>, dim3(gv), dim3(TB), 0, s, tree->parent, edge_valid, (int32_t)n, k,
-                     w[0], x.d[0]);
-  int cur = 0;  // ceil(log2 n) rounds, back to back
-  for (int64_t reach = 1; reach < n; reach <<= 1, cur ^= 1)
+  hipLaunchKernelGGL((k_keep_seed<DEPTH, GRAFT>), dim3(gv), dim3(TB), 0, s, tree->parent, edge_valid,
+                     x.attach, (int32_t)nv, k, w[0], x.d[0]);
+  int cur = 0;  // ceil(log2 nv) rounds, back to back
+  for (int64_t reach = 1; reach < nv; reach <<= 1, cur ^= 1)
     hipLaunchKernelGGL(k_keep_jump<DEPTH>, dim3(gv), dim3(TB), 0, s, w[cur], x.d[cur], w[cur ^ 1],
-                       x.d[cur ^ 1], (int32_t)n);
+                       x.d[cur ^ 1], (int32_t)nv);
   x.mark(1, s);
-  hipLaunchKernelGGL(k_keep_count<DEPTH>, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], x.d[cur],
-                     edge_valid, (int32_t)n, k, tile);
-  hipLaunchKernelGGL(k_keep_scan<DEPTH>, dim3(1), dim3(CB), 0, s, tile, ntile, toff, (int32_t)n, stats,
+  hipLaunchKernelGGL((k_keep_count<DEPTH, GRAFT>), dim3((unsigned)ntile), dim3(CB), 0, s, w[cur],
+                     x.d[cur], edge_valid, x.attach, (int32_t)nv, k, tile);
+  hipLaunchKernelGGL(k_keep_scan<DEPTH>, dim3(1), dim3(CB), 0, s, tile, ntile, toff, (int32_t)nv, kst,
                      fresh.count);
   if (hipGetLastError() != hipSuccess || hipMemsetAsync(fresh.hm, 0, 64, s) != hipSuccess ||
-      !x.before_rank(n, s))
+      !x.before_rank(nv, s))
     return drop_fresh(GBP_E_HIP);
-  hipLaunchKernelGGL(k_keep_rank<DEPTH>, dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], x.d[cur],
-                     (int32_t)n, k, toff, remap, x.depth, x.hist);
+  hipLaunchKernelGGL((k_keep_rank<DEPTH, GRAFT>), dim3((unsigned)ntile), dim3(CB), 0, s, w[cur], x.d[cur],
+                     (int32_t)nv, k, toff, remap, x.depth, x.hist);
   hipLaunchKernelGGL(k_prune_move_rows, dim3(grid_for(n * PRUNE_PIECES, TB, 2048)), dim3(TB), 0, s, *tree,
                      fresh, (int32_t)n, remap);
-  hipLaunchKernelGGL(k_prune_move_links, dim3(gv), dim3(TB), 0, s, *tree, fresh, (int32_t)n, remap);
+  hipLaunchKernelGGL(k_prune_move_links<GRAFT>, dim3(gv), dim3(TB), 0, s, *tree, fresh, (int32_t)n, remap,
+                     x.attach);
   if (hipGetLastError() != hipSuccess) return drop_fresh(GBP_E_HIP);
-  if ((rc = x.after_move(fresh, n, gv, stats, s))) return drop_fresh(rc);
+  if ((rc = x.after_move(fresh, nv, gv, kst, s))) return drop_fresh(rc);
   if (hipStreamSynchronize(s) != hipSuccess) return drop_fresh(GBP_E_HIP);
   tree_free_arrays(tree);
   (void)hipFree(tree->count);
@@ -506,10 +614,14 @@ int keep_host(gbp_terrain *t, gbp_tree *tree, int32_t k, int direction, int adap
   return GBP_OK;
 }
 
-// the last successful gbp_tree_reroot_dev of the process, for gbp_tree_reroot_last
-std::mutex reroot_last_mu;
-double reroot_last_ms[3] = {0, 0, 0};
-int64_t reroot_last_launches = 0;
+// the last successful gbp_tree_reroot_dev / gbp_tree_graft_dev of the process,
+// for gbp_tree_reroot_last / gbp_tree_graft_last
+struct LastCall {
+  double ms[3] = {0, 0, 0};
+  int64_t launches = 0;
+};
+std::mutex last_mu;
+LastCall reroot_last, graft_last;
 // the four marks between the call's three parts; a mark that could not be
 // created or recorded only leaves the times at zero
 struct RerootMarks {
@@ -531,7 +643,10 @@ struct RerootMarks {
 // call's three parts (keep rule | compaction, move and level sort | g) and
 // the launches made.
 struct RerootDepth {
-  static constexpr bool DEPTH = true;
+  static constexpr bool DEPTH = true, GRAFT = false;
+  using Stats = gbp_reroot_stats;
+  const uint8_t *attach = nullptr;
+  gbp_reroot_stats *keep_stats(gbp_reroot_stats *s) { return s; }
   uint32_t *d[2] = {nullptr, nullptr}, *depth = nullptr, *hist = nullptr, *first = nullptr;
   int32_t *order = nullptr;
   RerootMarks marks;
@@ -576,6 +691,159 @@ struct RerootDepth {
     return GBP_OK;
   }
 };
+
+// a finished call's times between its marks and its launches into `to`
+void keep_last(LastCall &to, const RerootDepth &x) {
+  std::lock_guard<std::mutex> lk(last_mu);
+  for (int q = 0; q < 3; q++) {
+    float t = 0.f;
+    to.ms[q] =
+        x.marks.ok && hipEventElapsedTime(&t, x.marks.e[q], x.marks.e[q + 1]) == hipSuccess ? t : 0.0;
+  }
+  to.launches = x.launches;
+}
+int read_last(const LastCall &from, double ms[3], int64_t *launches) {
+  if (!ms || !launches) return GBP_E_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(last_mu);
+  for (int k = 0; k < 3; k++) ms[k] = from.ms[k];
+  *launches = from.launches;
+  return GBP_OK;
+}
+
+// The graft's additions to the re-root's: the keep's record in a buffer of its
+// own (the call's is gbp_graft_stats), and after the move the attached
+// vertices hung under the new root and the root's row, list and record
+// (k_graft_attach, k_graft_root: before g is derived from them).  att, the
+// root's children in order, lives in `order` until k_reroot_order fills it.
+struct GraftRoot : RerootDepth {
+  static constexpr bool GRAFT = true;
+  using Stats = gbp_graft_stats;
+  const double *actions = nullptr;
+  const int32_t *remap = nullptr;
+  GraftState root{};
+  gbp_reroot_stats *rs = nullptr;
+  gbp_graft_stats *out = nullptr;
+  void carve(Stage &S, int64_t nv) {
+    RerootDepth::carve(S, nv);
+    S.take(rs, 1);
+  }
+  gbp_reroot_stats *keep_stats(gbp_graft_stats *s) {
+    out = s;
+    return rs;
+  }
+  int after_move(const gbp_tree &fresh, int64_t nv, unsigned gv, const gbp_reroot_stats *stats,
+                 hipStream_t s) {
+    launches += 2;
+    hipLaunchKernelGGL(k_graft_attach, dim3(gv), dim3(TB), 0, s, fresh, (int32_t)(nv - 1), remap, attach,
+                       actions);
+    hipLaunchKernelGGL(k_graft_root, dim3(1), dim3(CB), 0, s, fresh, root, order, rs, out);
+    HIPCHK(hipGetLastError());
+    return RerootDepth::after_move(fresh, nv, gv, stats, s);
+  }
+};
+
+bool has_nan8(const double *s) {
+  for (int k = 0; k < 8; k++)
+    if (s[k] != s[k]) return true;
+  return false;
+}
+
+// The synchronous graft: stage A on t, with test_edges the edges' decisions
+// as well (tree_edge_decisions), attach and the checks' flags back in one
+// copy, the FRAGILE checks re-decided with glibc from the vertex's own row
+// (attach and the action written back), then stage B.
+int graft_host(gbp_terrain *t, gbp_tree *tree, const double *root, double radius, int direction,
+               int adaptive, int test_edges, int32_t *remap, int32_t *remap_dev, int64_t remap_cap,
+               gbp_graft_stats *stats, int64_t *n_resolved) {
+  if (n_resolved) *n_resolved = 0;
+  if (!t || !tree_ok(tree)) return GBP_E_BAD_HANDLE;
+  if (!root || !stats || (direction != GBP_FORWARD && direction != GBP_REVERSE) || !(radius >= 0.0) ||
+      has_nan8(root))
+    return GBP_E_INVALID_ARG;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return GBP_E_NO_DEVICE;
+  if (!t->d_z) return GBP_E_BAD_HANDLE;
+  DeviceGuard g(tree->device);
+  hipStream_t s = t->host_stream;
+  int64_t n = 0;
+  int rc = gbp_tree_size(tree, &n, s);
+  if (rc) return rc;
+  if (remap_dev && n > remap_cap) return GBP_E_SHAPE;
+  if (remap_dev) {  // the caller keeps the device remap: it must lie on the tree's device
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, remap_dev) != hipSuccess || at.device != tree->device) {
+      (void)hipGetLastError();
+      return GBP_E_INVALID_ARG;
+    }
+  }
+  // attach and flags back to back, like edge_valid and its flags: one read-back each
+  const size_t fl_at = ((size_t)n + 255) & ~(size_t)255;
+  const size_t dec_bytes = fl_at + (size_t)n * sizeof(uint32_t);
+  DevBuf buf;
+  uint8_t *dchk, *dedge;
+  double *dact;
+  int32_t *dmap;
+  gbp_graft_stats *dst;
+  rc = stage_buf(buf, [&](Stage &S) {
+    S.take(dchk, dec_bytes);
+    S.take(dedge, test_edges ? dec_bytes : 0);
+    S.take(dact, 10 * n);
+    S.take(dmap, remap_dev ? 0 : n);
+    S.take(dst, 1);
+  });
+  if (rc) return rc;
+  if (remap_dev) dmap = remap_dev;
+  rc = gbp_tree_graft_check_dev(t, tree, n, root, radius, direction, adaptive, dchk, dact,
+                                (uint32_t *)(dchk + fl_at), s);
+  if (rc) return rc;
+  int64_t resolved = 0;
+  if (test_edges && (rc = tree_edge_decisions(t, tree, n, direction, adaptive, dedge, fl_at, &resolved, s)))
+    return rc;
+  std::vector<uint8_t> chk(dec_bytes);
+  if ((rc = d2h(chk.data(), dchk, dec_bytes, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  uint8_t *att = chk.data();
+  const uint32_t *fl = (const uint32_t *)(chk.data() + fl_at);
+  int64_t candidates = 0, checked = 0, redone = 0;
+  for (int64_t j = 0; j < n; j++) {
+    candidates += (fl[j] & GBP_F_GRAFT_CANDIDATE) != 0;
+    checked += (fl[j] & GBP_F_GRAFT_CHECKED) != 0;
+    if (!(fl[j] & GBP_F_FRAGILE)) continue;
+    // depth 0 of attemptConnect(r, v[j]) again with glibc (host/gbp_host_check.cpp)
+    const gbp_host::Terrain *H = host_mirror(t);
+    if (!H) return GBP_E_HIP;
+    double sj[8], a[10], sn[8], tn = 0;
+    if ((rc = d2h(sj, tree->v + 8 * j, 8, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const double t_s = gbp_host::pose_distance(sj, root) / V_NOM;
+    bool ok = false;
+    if (t_s > KINEMATICS_RES) {
+      gbp_host::connect_action(direction == GBP_FORWARD ? root : sj, direction == GBP_FORWARD ? sj : root,
+                               t_s, a);
+      if (gbp_host::is_valid_action(a)) {
+        uint32_t f = 0;
+        ok = gbp_host::pair_check(*H, root, a, direction, adaptive, sn, &tn, &f, nullptr);
+        if ((rc = h2d(dact + 10 * j, a, 10, s))) return rc;
+        HIPCHK(hipStreamSynchronize(s));  // a leaves scope only after the copy
+      }
+    }
+    att[j] = ok ? 1 : 0;
+    redone++;
+  }
+  if (redone) {
+    if ((rc = h2d(dchk, att, n, s))) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  rc = gbp_tree_graft_dev(tree, n, root, dchk, dact, test_edges ? dedge : nullptr, dmap, dst, s);
+  if (rc) return rc;
+  if (remap && (rc = d2h(remap, dmap, n, s))) return rc;
+  if ((rc = d2h(stats, dst, 1, s))) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  stats->n_candidates = candidates;
+  stats->n_checked = checked;
+  if (n_resolved) *n_resolved = resolved + redone;
+  return GBP_OK;
+}
 
 }  // namespace
 
@@ -625,11 +893,7 @@ int gbp_tree_revalidate_keep_host(gbp_terrain *t, gbp_tree *tree, int direction,
 
 // ---- re-rooting at a vertex ---------------------------------------
 int gbp_tree_reroot_last(double ms[3], int64_t *launches) {
-  if (!ms || !launches) return GBP_E_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(reroot_last_mu);
-  for (int k = 0; k < 3; k++) ms[k] = reroot_last_ms[k];
-  *launches = reroot_last_launches;
-  return GBP_OK;
+  return read_last(reroot_last, ms, launches);
 }
 
 int gbp_tree_reroot_dev(gbp_tree *tree, int64_t n, int32_t new_root, const uint8_t *edge_valid,
@@ -637,13 +901,7 @@ int gbp_tree_reroot_dev(gbp_tree *tree, int64_t n, int32_t new_root, const uint8
   RerootDepth x;
   const int rc = tree_keep(tree, n, new_root, edge_valid, remap, stats, (hipStream_t)stream, x);
   if (rc) return rc;
-  std::lock_guard<std::mutex> lk(reroot_last_mu);
-  for (int q = 0; q < 3; q++) {
-    float t = 0.f;
-    reroot_last_ms[q] =
-        x.marks.ok && hipEventElapsedTime(&t, x.marks.e[q], x.marks.e[q + 1]) == hipSuccess ? t : 0.0;
-  }
-  reroot_last_launches = x.launches;
+  keep_last(reroot_last, x);
   return GBP_OK;
 }
 
@@ -657,6 +915,40 @@ int gbp_tree_reroot_keep_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, 
                               gbp_reroot_stats *stats, int64_t *n_resolved) {
   return keep_host<true>(t, tree, new_root, direction, adaptive, remap, remap_dev, remap_cap, stats,
                          n_resolved);
+}
+
+// ---- grafting onto a root state that is no vertex -------------------
+int gbp_tree_graft_last(double ms[3], int64_t *launches) { return read_last(graft_last, ms, launches); }
+
+int gbp_tree_graft_dev(gbp_tree *tree, int64_t n, const double *root, const uint8_t *attach,
+                       const double *actions, const uint8_t *edge_valid, int32_t *remap,
+                       gbp_graft_stats *stats, gbp_stream stream) {
+  if (!tree_ok(tree)) return GBP_E_BAD_HANDLE;
+  if (!root || !attach || !actions || has_nan8(root)) return GBP_E_INVALID_ARG;
+  GraftRoot x;
+  x.attach = attach;
+  x.actions = actions;
+  x.remap = remap;
+  for (int k = 0; k < 8; k++) x.root.s[k] = root[k];
+  const int rc = tree_keep(tree, n, 0, edge_valid, remap, stats, (hipStream_t)stream, x);
+  if (rc) return rc;
+  keep_last(graft_last, x);
+  return GBP_OK;
+}
+
+int gbp_tree_graft_host(gbp_terrain *t, gbp_tree *tree, const double *root, double radius,
+                        int direction, int adaptive, int test_edges, int32_t *remap,
+                        gbp_graft_stats *stats, int64_t *n_resolved) {
+  return graft_host(t, tree, root, radius, direction, adaptive, test_edges, remap, nullptr, 0, stats,
+                    n_resolved);
+}
+
+int gbp_tree_graft_keep_host(gbp_terrain *t, gbp_tree *tree, const double *root, double radius,
+                             int direction, int adaptive, int test_edges, int32_t *remap,
+                             int32_t *remap_dev, int64_t remap_cap, gbp_graft_stats *stats,
+                             int64_t *n_resolved) {
+  return graft_host(t, tree, root, radius, direction, adaptive, test_edges, remap, remap_dev, remap_cap,
+                    stats, n_resolved);
 }
 
 }  // extern "C"

@@ -1421,6 +1421,72 @@ void RRTConnectClass::rerootStartTree(FastTerrainMap &terrain, TreeDump &trees, 
   if (remap) *remap = std::move(map);
 }
 
+static GraftStats graft_stats_of(const gbp_graft_stats &gs, int64_t fragile_resolved) {
+  GraftStats done;
+  done.n_before = gs.n_before;
+  done.n_kept = gs.n_kept;
+  done.n_candidates = gs.n_candidates;
+  done.n_checked = gs.n_checked;
+  done.n_attached = gs.n_attached;
+  done.n_outside = gs.n_outside;
+  done.n_edge_invalid = gs.n_edge_invalid;
+  done.n_inherited = gs.n_inherited;
+  done.depth = gs.depth;
+  done.fragile_resolved = fragile_resolved;
+  return done;
+}
+
+void RRTConnectClass::graftStartTree(FastTerrainMap &terrain, TreeDump &trees, const State &s,
+                                     double radius, GraftStats &stats, std::vector<int32_t> *remap,
+                                     bool test_edges) {
+  struct Tree {  // the device tree of this call
+    gbp_tree *t = nullptr;
+    ~Tree() {
+      if (t) gbp_tree_destroy(t);
+    }
+  };
+  const int64_t n = (int64_t)trees.v[0].size();
+  if (n < 1 || (int64_t)trees.a[0].size() != n || (int64_t)trees.parent[0].size() != n ||
+      (int64_t)trees.g[0].size() != n)
+    throw EngineError(GBP_E_INVALID_ARG, "graftStartTree: tree arrays");
+  Tree T;
+  chk(gbp_tree_create(terrain.device(), n + 1, &T.t), "graftStartTree: tree");
+  chk(gbp_tree_load_host(T.t, n, trees.v[0][0].data(), trees.a[0][0].data(), trees.parent[0].data(),
+                         nullptr),
+      "graftStartTree: tree load");
+  std::vector<int32_t> map(n);
+  gbp_graft_stats gs{};
+  int64_t resolved = 0;
+  chk(gbp_tree_graft_host(terrain.handle(), T.t, s.data(), radius, FORWARD,
+                          state_action_pair_check_adaptive_step_size_flag_ ? 1 : 0, test_edges ? 1 : 0,
+                          map.data(), &gs, &resolved),
+      "graftStartTree");
+  const GraftStats done = graft_stats_of(gs, resolved);
+  // the device's parents and actions tell which vertices were attached and by
+  // what; the survivors then come from the host copy (the device moved the
+  // same rows), g from the device: it is derived again there
+  std::vector<int32_t> dp((size_t)done.n_kept);
+  std::vector<Action> da((size_t)done.n_kept);
+  std::vector<double> dg((size_t)done.n_kept);
+  chk(gbp_tree_read(T.t, 0, done.n_kept, nullptr, da[0].data(), dp.data(), dg.data(), nullptr),
+      "graftStartTree: rows");
+  std::vector<uint8_t> attach((size_t)n, 0);
+  std::vector<Action> actions((size_t)n);
+  for (int64_t i = 0; i < n; i++) {
+    actions[i].fill(0.0);
+    if (map[i] < 1 || map[i] >= done.n_kept || dp[map[i]] != 0) continue;
+    attach[i] = 1;
+    actions[i] = da[map[i]];
+  }
+  TreeDump kept = trees;
+  if (!applyGraftRemap(map, s, attach, actions, kept, 0) || (int64_t)kept.v[0].size() != done.n_kept)
+    throw EngineError(GBP_E_INVALID_ARG, "graftStartTree: remap");
+  kept.g[0] = std::move(dg);
+  trees = std::move(kept);
+  stats = done;
+  if (remap) *remap = std::move(map);
+}
+
 bool RRTConnectClass::buildRRTConnectBatched(FastTerrainMap &terrain, State s_start, State s_goal,
                                              int batch, double max_time,
                                              std::vector<State> &state_sequence,
@@ -2379,6 +2445,48 @@ void ReplanSession::robotAt(const State &s, RerootStats &stats, SharedStats *sha
   if (vertex < 0)
     throw EngineError(GBP_E_INVALID_ARG, "ReplanSession: the state is no start-tree vertex of the path");
   robotAt(vertex, stats, shared, test_edges);
+}
+
+// tree k grafted onto s where it is, the list carried through that remap (the
+// other side's indices stay) and ranked again
+bool ReplanSession::graftTree(int k, const State &s, double radius, GraftStats &stats,
+                              SharedStats *shared, bool test_edges) {
+  Impl &I = impl();
+  DeviceSearch &S = I.S;
+  chk(gbp_stream_synchronize(S.stream), "stream");
+  // the new root is tested before anything changes: a start in STANCE, a goal
+  // in STANCE or in FLIGHT (a goal root may be FLIGHT-valid only)
+  bool ok = false;
+  for (int phase : {STANCE, FLIGHT}) {
+    if (ok || (k == 0 && phase == FLIGHT)) continue;
+    uint8_t v = 0;
+    chk(gbp_valid_states_host(S.h, 1, s.data(), nullptr, phase, &v, nullptr, nullptr),
+        "ReplanSession: root state");
+    ok = v != 0;
+  }
+  if (!ok) return false;
+  const int64_t before[2] = {S.known[0], S.known[1]};
+  I.remap[k].reserve(I.device, before[k], sizeof(int32_t), 1 << 12, "ReplanSession: remap");
+  gbp_graft_stats gs{};
+  int64_t resolved = 0;
+  chk(gbp_tree_graft_keep_host(S.h, S.tree[k], s.data(), radius, k == 0 ? FORWARD : REVERSE, S.adaptive,
+                               test_edges ? 1 : 0, nullptr, I.remap[k].data<int32_t>(),
+                               I.remap[k].capacity(), &gs, &resolved),
+      "ReplanSession: graft");
+  S.known[k] = gs.n_kept;
+  stats = graft_stats_of(gs, resolved);
+  carryShared(k == 0, k == 1, before, shared);
+  return true;
+}
+
+bool ReplanSession::robotOff(const State &s, double radius, GraftStats &stats, SharedStats *shared,
+                             bool test_edges) {
+  return graftTree(0, s, radius, stats, shared, test_edges);
+}
+
+bool ReplanSession::goalAt(const State &s, double radius, GraftStats &stats, SharedStats *shared,
+                           bool test_edges) {
+  return graftTree(1, s, radius, stats, shared, test_edges);
 }
 
 bool ReplanSession::bestPath(std::vector<State> &state_sequence,

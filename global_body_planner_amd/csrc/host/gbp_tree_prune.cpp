@@ -91,4 +91,47 @@ bool applyRerootRemap(const std::vector<int32_t> &remap, int32_t new_root, TreeD
   return true;
 }
 
+bool applyGraftRemap(const std::vector<int32_t> &remap, const State &root,
+                     const std::vector<uint8_t> &attach, const std::vector<Action> &actions,
+                     TreeDump &trees, int k) {
+  const size_t n = remap.size();
+  if (k < 0 || k > 1 || n < 1 || attach.size() != n || actions.size() != n || trees.v[k].size() != n ||
+      trees.a[k].size() != n || trees.parent[k].size() != n || trees.g[k].size() != n)
+    return false;
+  const std::vector<int32_t> &parent = trees.parent[k];
+  // the whole map is checked before the first row moves
+  int64_t kept = 1;
+  for (size_t i = 0; i < n; i++) {
+    if (remap[i] < 0) {
+      if (attach[i]) return false;
+      continue;
+    }
+    if (remap[i] != kept) return false;
+    if (!attach[i] && (parent[i] < 0 || (size_t)parent[i] >= n || remap[parent[i]] < 0)) return false;
+    kept++;
+  }
+  // out of place: with every vertex kept the rows move up by one
+  std::vector<State> v((size_t)kept);
+  std::vector<Action> a((size_t)kept);
+  std::vector<int32_t> p((size_t)kept);
+  std::vector<double> g((size_t)kept);
+  v[0] = root;
+  a[0].fill(0.0);
+  p[0] = -1;
+  g[0] = 0.0;
+  for (size_t i = 0; i < n; i++) {
+    const int64_t j = remap[i];
+    if (j < 0) continue;
+    v[j] = trees.v[k][i];
+    a[j] = attach[i] ? actions[i] : trees.a[k][i];
+    p[j] = attach[i] ? 0 : remap[parent[i]];
+    g[j] = trees.g[k][i];
+  }
+  trees.v[k] = std::move(v);
+  trees.a[k] = std::move(a);
+  trees.parent[k] = std::move(p);
+  trees.g[k] = std::move(g);
+  return true;
+}
+
 }  // namespace gbp_amd

@@ -1,6 +1,6 @@
-// gbp_tree_prune.h — a prune's remap (gbp_tree_prune_dev, include/gbp.h) or a
-// re-root's (gbp_tree_reroot_dev) applied to the host copy of a tree.  Pure
-// host code with no engine call.
+// gbp_tree_prune.h — a prune's remap (gbp_tree_prune_dev, include/gbp.h), a
+// re-root's (gbp_tree_reroot_dev) or a graft's (gbp_tree_graft_dev) applied to
+// the host copy of a tree.  Pure host code with no engine call.
 #pragma once
 
 #include <cstdint>
@@ -35,5 +35,18 @@ int64_t applyRerootRemap(const int32_t *remap, int64_t n, int32_t new_root, Stat
 
 // tree k of a TreeDump (its four vectors shortened to the survivors)
 bool applyRerootRemap(const std::vector<int32_t> &remap, int32_t new_root, TreeDump &trees, int k);
+
+// remap[n] as the device graft returns it: the kept vertices numbered 1, 2, ...
+// in ascending old index (0 is the new root state, no vertex of the tree),
+// every attached vertex (attach[i] != 0) kept, every other kept vertex under a
+// kept parent.  Tree k of `trees` becomes the root (its action zeroed, its
+// parent -1, g 0) followed by the kept rows: an attached vertex under vertex 0
+// by actions[i], the others under remap[parent] by their own action.  g's rows
+// are moved as they are: a graft derives g again, and the caller takes it from
+// the device tree.  False, with nothing changed, when remap is no such map for
+// these parents and this attach.
+bool applyGraftRemap(const std::vector<int32_t> &remap, const State &root,
+                     const std::vector<uint8_t> &attach, const std::vector<Action> &actions,
+                     TreeDump &trees, int k);
 
 }  // namespace gbp_amd

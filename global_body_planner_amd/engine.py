@@ -547,6 +547,71 @@ class DeviceTree:
         stats["n_resolved"] = k.value
         return remap, stats
 
+    def graft(self, root, radius, terrain, direction, adaptive=False, test_edges=False,
+              remap_dev=None):
+        """gbp_tree_graft_host: makes the state `root`, which need not be a
+        vertex, the tree's root, in HBM.  Every vertex within `radius`
+        (poseDistance) that `root` connects to directly on `terrain` (depth 0
+        of attemptConnect(root, v, direction) is REACHED) becomes a child of the
+        new root by that connect action; a vertex stays when such a vertex
+        lies on its parent chain (itself included) and, with test_edges, every
+        edge up to the nearest one still holds on `terrain`.  The root becomes
+        vertex 0, the kept vertices follow in ascending old index, g is
+        derived again.  Nothing attached leaves the root alone.  Returns
+        (remap, stats): remap [n before] int32; stats a dict of n_before,
+        n_kept, n_candidates, n_checked, n_attached, n_outside,
+        n_edge_invalid, n_inherited, depth and n_resolved.  remap_dev: as in
+        revalidate (gbp_tree_graft_keep_host)."""
+        r = np.ascontiguousarray(root, np.float64).reshape(8)
+        remap = np.empty(len(self), np.int32)
+        st = L.GraftStats()
+        k = ctypes.c_int64(0)
+        args = (terrain._h, self._h, _np_ptr(r), float(radius), int(direction), int(bool(adaptive)),
+                int(bool(test_edges)), _np_ptr(remap))
+        if remap_dev is not None:
+            check(self._lib.gbp_tree_graft_keep_host(*args, _ptr(remap_dev), remap_dev.numel(),
+                                                     ctypes.byref(st), ctypes.byref(k)),
+                  "tree_graft_keep")
+        else:
+            check(self._lib.gbp_tree_graft_host(*args, ctypes.byref(st), ctypes.byref(k)),
+                  "tree_graft")
+        stats = {name: getattr(st, name) for name, _ in L.GraftStats._fields_}
+        stats["n_resolved"] = k.value
+        return remap, stats
+
+    def graft_check(self, root, radius, terrain, direction, adaptive=False):
+        """gbp_tree_graft_check_dev, the graft's stage A, on torch's current
+        stream: (attach uint8 [n], actions float64 [n, 10], flags int32 [n])
+        device tensors.  actions[j] is written where flags[j] has
+        F_GRAFT_CHECKED (the rest is zero); a FRAGILE flag is the caller's to
+        re-decide."""
+        n = len(self)
+        dev = terrain.torch_device
+        r = np.ascontiguousarray(root, np.float64).reshape(8)
+        attach = torch.zeros(n, dtype=torch.uint8, device=dev)
+        actions = torch.zeros((n, 10), dtype=torch.float64, device=dev)
+        flags = torch.zeros(n, dtype=torch.int32, device=dev)
+        check(self._lib.gbp_tree_graft_check_dev(terrain._h, self._h, n, _np_ptr(r), float(radius),
+                                                 int(direction), int(bool(adaptive)), _ptr(attach),
+                                                 _ptr(actions), _ptr(flags), _stream(self.device)),
+              "tree_graft_check")
+        return attach, actions, flags
+
+    def graft_apply(self, root, attach, actions, edge_valid=None):
+        """gbp_tree_graft_dev, the graft's stage B, under the caller's
+        decisions: device tensors attach uint8 [n], actions float64 [n, 10],
+        edge_valid uint8 [n] or None.  Returns (remap, stats) as graft does
+        (n_candidates = n_checked = 0, no n_resolved)."""
+        n = len(self)
+        r = np.ascontiguousarray(root, np.float64).reshape(8)
+        remap = torch.empty(n, dtype=torch.int32, device=attach.device)
+        st = torch.zeros(len(L.GraftStats._fields_), dtype=torch.int64, device=attach.device)
+        check(self._lib.gbp_tree_graft_dev(self._h, n, _np_ptr(r), _ptr(attach), _ptr(actions),
+                                           _ptr(edge_valid), _ptr(remap), _ptr(st),
+                                           _stream(self.device)), "tree_graft_dev")
+        names = [name for name, _ in L.GraftStats._fields_]
+        return remap.cpu().numpy(), dict(zip(names, st.cpu().tolist()))
+
     def capacity(self):
         c = ctypes.c_int64(0)
         check(self._lib.gbp_tree_capacity(self._h, ctypes.byref(c)), "tree_capacity")

@@ -414,6 +414,39 @@ def reroot_tree(tree, vertex, data=None, adaptive=False, device=0):
     return dict(v=s, act=a, parent=p, g=g), remap, stats
 
 
+def graft_tree(tree, root, radius, data, direction=_lib.FORWARD, adaptive=False, test_edges=False,
+               device=0):
+    """A tree of an earlier search once its root has moved to a state that is
+    none of its vertices (the robot part of the way through an action or off
+    its plan: tree a, FORWARD; a goal that moved: tree b, REVERSE): what of it
+    the next search, from `root`, may start from.
+
+    tree: a dict of v [n][8], act [n][10], parent [n].  It is loaded into HBM
+    and grafted there (engine.DeviceTree.graft) on `data`
+    (terrain_data.TerrainData, or an engine.Terrain): every vertex within
+    `radius` that `root` connects to directly becomes a child of `root` by that
+    connect action, and a vertex stays when such a vertex lies on its parent
+    chain; with test_edges the map has changed too and every edge up to the
+    nearest attached vertex must hold on it.  `root` itself is not tested.
+    Returns (tree, remap, stats): `root` as vertex 0 and the survivors as a
+    dict of v, act, parent and g (derived again), the int32 map from an old
+    index to the new one (-1: dropped), the stats dict."""
+    from . import engine
+    own = not isinstance(data, engine.Terrain)
+    T = engine.Terrain.from_data(data, device=device) if own else data
+    try:
+        v = np.ascontiguousarray(tree["v"], np.float64).reshape(-1, 8)
+        dt = engine.DeviceTree(v[0], device=T.device, capacity=v.shape[0] + 1)
+        dt.load(v, tree["act"], tree["parent"])
+        remap, stats = dt.graft(root, radius, T, direction, adaptive=adaptive, test_edges=test_edges)
+        s, a, p, g = dt.read()
+        del dt
+    finally:
+        if own:
+            T.close()
+    return dict(v=s, act=a, parent=p, g=g), remap, stats
+
+
 def attempt_connect(terrain, s_existing, s, direction, t_s=None, adaptive=False, s_new=None,
                     a_new=None):
     """RRTConnectClass::attemptConnect (rrt_connect.cpp:20-91) for n pairs on an
@@ -617,6 +650,37 @@ class ReplanSession:
                                      self.adaptive, remap_dev=buf)[1]
         self.known[0] = stats["n_kept"]
         return stats, self._carry(buf, None, before)
+
+    def _graft(self, k, s, radius, test_edges):
+        s = np.ascontiguousarray(s, np.float64).reshape(8)
+        # the new root is tested before anything changes: a start in STANCE, a
+        # goal in STANCE or in FLIGHT (a goal root may be FLIGHT-valid only)
+        phases = (_lib.STANCE,) if k == 0 else (_lib.STANCE, _lib.FLIGHT)
+        if not any(self.T.valid_states_host(s[None], ph)[0][0] for ph in phases):
+            return None
+        before = list(self.known)
+        buf = self._remap_buf(k, before[k])
+        stats = self.trees[k].graft(s, radius, self.T, _lib.FORWARD if k == 0 else _lib.REVERSE,
+                                    self.adaptive, test_edges=test_edges, remap_dev=buf)[1]
+        self.known[k] = stats["n_kept"]
+        return stats, self._carry(buf if k == 0 else None, buf if k == 1 else None, before)
+
+    def robot_off(self, s, radius, test_edges=False):
+        """The robot stands on state `s` ([8] values), which need not be a
+        vertex: the start tree is grafted onto it (engine.DeviceTree.graft,
+        FORWARD, the vertices within `radius` checked) and the list carried
+        through that remap and ranked again.  `s` is tested first (STANCE):
+        returns None, with nothing changed, when it fails; else (graft stats,
+        shared stats).  With nothing attached the start tree is `s` alone and
+        the list empty."""
+        self._need()
+        return self._graft(0, s, radius, test_edges)
+
+    def goal_at(self, s, radius, test_edges=False):
+        """The goal moved to state `s`: robot_off's operation on the goal tree
+        (REVERSE); `s` may be valid in STANCE or in FLIGHT."""
+        self._need()
+        return self._graft(1, s, radius, test_edges)
 
     # -- what the search holds --------------------------------------------------------
     def best_path(self):

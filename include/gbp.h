@@ -645,6 +645,96 @@ int gbp_tree_reroot_keep_host(gbp_terrain *t, gbp_tree *tree, int32_t new_root, 
                               int adaptive, int32_t *remap, int32_t *remap_dev, int64_t remap_cap,
                               gbp_reroot_stats *stats, int64_t *n_resolved);
 
+/* ---- a tree grafted onto a root that is not one of its vertices -------------------
+ * The robot is part of the way through an action or has drifted off its plan
+ * (or, on the reverse-grown goal tree, the goal has moved): the next search
+ * starts from a state r that no vertex holds.  What it may reuse of a tree
+ * grown in `direction` are the vertices r connects to directly and what hangs
+ * below them.  (Ours: the reference has no such operation.)
+ *   candidates  vertex j with poseDistance(r, v[j]) <= radius, compared as
+ *               neighborhoodDist compares (radius = INFINITY: every vertex)
+ *   attached    a candidate for which depth 0 of attemptConnect(s_existing = r,
+ *               s = v[j], t_s = poseDistance(v[j], r) / V_NOM, direction)
+ *               (rrt_connect.cpp:20-75) is REACHED: t_s > KINEMATICS_RES, the
+ *               connect action valid, the pair check from r in `direction`
+ *               valid — the check RRT*'s rewire makes.  v[j] is not compared
+ *               with the check's s_new; a vertex whose state equals r has
+ *               t_s = 0 and is not attached (that root is gbp_tree_reroot_*'s)
+ *   parents     every attached vertex becomes a child of r, its action the
+ *               connect action, also when one of its ancestors is attached
+ *   kept        vertex i when its parent chain, i included, holds an attached
+ *               vertex and every edge from i up to but excluding the nearest
+ *               such vertex j has edge_valid = 1 (j's own old edge is ignored):
+ *               the re-root's rule at vertex n of the tree of n + 1 vertices
+ *               whose vertex n is r and whose attached vertices have parent n
+ * r becomes vertex 0 (ten zero action values, parent -1, as gbp_tree_init
+ * writes them), the kept vertices follow in ascending old index, g is derived
+ * again from r down as gbp_tree_load_host derives it; a tree whose parents
+ * precede their children has them so again.  With nothing attached the tree
+ * is r alone: an answer, not an error.  r itself is never tested (callers test
+ * roots with gbp_valid_states_*). */
+typedef struct {
+  int64_t n_before;        /* vertices of the tree before the call                   */
+  int64_t n_kept;          /* ... and after it, the new root included                */
+  int64_t n_candidates;    /* vertices within the radius        (0 from stage B:     */
+  int64_t n_checked;       /* pair checks run                    the _host entries   */
+                           /*                                    count stage A's)    */
+  int64_t n_attached;      /* children of the new root                               */
+  int64_t n_outside;       /* dropped: no attached vertex on the parent chain        */
+  int64_t n_edge_invalid;  /* dropped: below one, not attached, own edge failed      */
+  int64_t n_inherited;     /* dropped: below one, only because an ancestor was       */
+  int64_t depth;           /* most edges between the new root and a kept vertex      */
+} gbp_graft_stats;
+#define GBP_F_GRAFT_CANDIDATE (1u << 16) /* stage A: the vertex lies within the radius     */
+#define GBP_F_GRAFT_CHECKED   (1u << 17) /* stage A: its connect action had a pair check   */
+/* Stage A: which vertices r attaches.  n = the tree's size (GBP_E_SHAPE when
+ * it is not the device's count: the call reads it, which synchronises the
+ * stream); host root[8]; device attach[n] (1 = attached), actions[n][10] (row
+ * j written when vertex j's check ran: the connect action), flags[n] (the
+ * check's GBP_F_* word, 0 without one, | GBP_F_GRAFT_CANDIDATE |
+ * GBP_F_GRAFT_CHECKED).  One launch, one wave per vertex: the distance test
+ * decides whether the wave goes on to the action and the pair check.  A
+ * FRAGILE decision is left to the caller, as in gbp_tree_revalidate_dev.
+ * GBP_E_INVALID_ARG for a bad direction, NaN in root, a negative or NaN radius. */
+int gbp_tree_graft_check_dev(gbp_terrain *t, gbp_tree *tree, int64_t n, const double *root,
+                             double radius, int direction, int adaptive, uint8_t *attach,
+                             double *actions, uint32_t *flags, gbp_stream stream);
+/* Stage B: the graft under the caller's decisions.  Host root[8]; device
+ * attach[n] (non-zero = attached), actions[n][10] (read at attached vertices),
+ * edge_valid[n] (NULL: every edge holds), remap[n] = a vertex's new index or
+ * -1, stats[1] (n_candidates = n_checked = 0).  Attached vertices get parent 0
+ * and their row of `actions`, every other kept vertex remap[parent] and its
+ * old action; the fp16 search rows, the search bounds and the successor lists
+ * are rebuilt from the kept rows (attached vertices leave their old parent's
+ * list and form the root's, in ascending index; the other lists keep their
+ * order); the count is set.  When n + 1 exceeds the capacity the fresh arrays
+ * are larger (at least twice the capacity).  As in gbp_tree_reroot_dev
+ * everything goes into fresh arrays and the swap is the last step: a call that
+ * returns an error leaves the tree as it was.  Synchronises the stream as
+ * gbp_tree_reroot_dev does.  GBP_E_SHAPE when n is not the device's count,
+ * GBP_E_INVALID_ARG for NaN in root. */
+int gbp_tree_graft_dev(gbp_tree *tree, int64_t n, const double *root, const uint8_t *attach,
+                       const double *actions, const uint8_t *edge_valid, int32_t *remap,
+                       gbp_graft_stats *stats, gbp_stream stream);
+/* Diagnostics (tools/tree_graft_ab.py): gbp_tree_reroot_last's figures of the
+ * process's last successful gbp_tree_graft_dev. */
+int gbp_tree_graft_last(double ms[3], int64_t *launches);
+/* Both stages, synchronous, on the terrain's own stream: stage A; with
+ * test_edges also the edges' decisions on t (gbp_tree_revalidate_dev: the map
+ * has changed and the robot is off the tree, in one pass); one read-back of
+ * the flags; the FRAGILE checks re-decided with glibc (*n_resolved, may be
+ * NULL); stage B.  Host remap[size of the tree before] (may be NULL) and
+ * stats[1], n_candidates and n_checked counted from stage A's flags. */
+int gbp_tree_graft_host(gbp_terrain *t, gbp_tree *tree, const double *root, double radius,
+                        int direction, int adaptive, int test_edges, int32_t *remap,
+                        gbp_graft_stats *stats, int64_t *n_resolved);
+/* The same, with the remap also left in the caller's device array
+ * remap_dev[remap_cap], as gbp_tree_reroot_keep_host leaves the re-root's. */
+int gbp_tree_graft_keep_host(gbp_terrain *t, gbp_tree *tree, const double *root, double radius,
+                             int direction, int adaptive, int test_edges, int32_t *remap,
+                             int32_t *remap_dev, int64_t remap_cap, gbp_graft_stats *stats,
+                             int64_t *n_resolved);
+
 /* ---- the device planner loop (RRTConnectClass::runRRTConnect,
  *      rrt_connect.cpp:230-314, batch-synchronous) ---------------------------
  * One half-iteration, enqueued on `stream` without any host synchronisation:

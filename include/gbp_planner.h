@@ -530,6 +530,22 @@ struct RerootStats {
   int64_t fragile_resolved = 0;
 };
 
+// What RRTConnectClass::graftStartTree and ReplanSession::robotOff / goalAt
+// did (gbp_graft_stats, include/gbp.h, and the FRAGILE checks and edges
+// re-decided on the host with glibc).
+struct GraftStats {
+  int64_t n_before = 0;        // vertices of the tree before
+  int64_t n_kept = 0;          // ... and after: the new root and what hangs below it
+  int64_t n_candidates = 0;    // vertices within the radius of the new root
+  int64_t n_checked = 0;       // pair checks run for them
+  int64_t n_attached = 0;      // children of the new root
+  int64_t n_outside = 0;       // dropped: no attached vertex on the parent chain
+  int64_t n_edge_invalid = 0;  // dropped: below one, own edge failed on the map
+  int64_t n_inherited = 0;     // dropped: below one, only because an ancestor was
+  int64_t depth = 0;           // most edges between the new root and a kept vertex
+  int64_t fragile_resolved = 0;
+};
+
 class RRTConnectClass : public RRTClass {
  public:
   // rrt_connect.cpp:20-84 (recursive; the pair checks run on the engine)
@@ -629,6 +645,23 @@ class RRTConnectClass : public RRTClass {
   // (EngineError) leaves trees, stats and remap as they were.
   void rerootStartTree(FastTerrainMap &terrain, TreeDump &trees, int32_t vertex, RerootStats &stats,
                        std::vector<int32_t> *remap = nullptr, bool test_edges = false);
+
+  // The robot is off the tree: at the next call it stands on state `s`, which
+  // need not be a vertex (part of the way through an action, or drifted off
+  // the plan).  Tree 0 of `trees` is loaded into HBM and grafted there
+  // (gbp_tree_graft_host, FORWARD): every vertex within `radius` that s
+  // connects to directly on `terrain` becomes a child of s by that connect
+  // action, and a vertex stays when such a vertex lies on its parent chain
+  // (with test_edges: and every edge up to the nearest one holds on
+  // `terrain`).  Tree 0 is left holding s as vertex 0 and the survivors in
+  // ascending old index with g derived again, ready for BatchStats::warm_* of a
+  // search from s; with nothing attached it holds s alone.  s itself is the
+  // caller's to test (isValidState).  tree 1 is not touched.  remap (optional)
+  // receives each old vertex's new index or -1.  A call that throws
+  // (EngineError) leaves trees, stats and remap as they were.
+  void graftStartTree(FastTerrainMap &terrain, TreeDump &trees, const State &s, double radius,
+                      GraftStats &stats, std::vector<int32_t> *remap = nullptr,
+                      bool test_edges = false);
 
   // attemptConnect for many independent pairs (lock-step rounds, one engine
   // launch per recursion depth); s_new / a_new are in/out per pair
@@ -767,6 +800,16 @@ struct SharedStats {
 //              (startTreePath) and takes the first path state equal to s bit
 //              for bit, as findStateAmong does on a dumped tree.  A caller
 //              that tracks vertex indices should pass the vertex.
+//   robotOff   the robot stands on a state that is no vertex: the start tree
+//              is grafted onto it (gbp_tree_graft_keep_host, FORWARD, the
+//              vertices within `radius` checked), with test_edges its edges
+//              tested on the map as well, and the list carried through that
+//              remap and ranked again (g has changed).  s is tested first,
+//              isValidState(s, STANCE): false, with nothing changed, when it
+//              fails.  With nothing attached the start tree is s alone and the
+//              list empty: the next search grows it again.
+//   goalAt     the same for a goal that moved, on the goal tree (REVERSE); s
+//              may be valid in STANCE or in FLIGHT, as a goal root may be.
 //   search's BatchStats: halves and iterations are added per call; rewires,
 //              solutions, targets, extends, attempts_checked, connects,
 //              fragile_resolved, depth_capped, vertices_* and meet_* are set
@@ -795,6 +838,10 @@ class ReplanSession : public RRTStarConnectClass {
                bool test_edges = false);
   void robotAt(const State &s, RerootStats &stats, SharedStats *shared = nullptr,
                bool test_edges = false);
+  bool robotOff(const State &s, double radius, GraftStats &stats, SharedStats *shared = nullptr,
+                bool test_edges = false);
+  bool goalAt(const State &s, double radius, GraftStats &stats, SharedStats *shared = nullptr,
+              bool test_edges = false);
   bool bestPath(std::vector<State> &state_sequence, std::vector<Action> &action_sequence);
   void dump(TreeDump &trees);
   // the kept connections in list order; best (optional): {best_a, best_b} or {-1, -1}
@@ -810,6 +857,8 @@ class ReplanSession : public RRTStarConnectClass {
   Impl *impl_ = nullptr;
   Impl &impl() const;  // throws EngineError(GBP_E_BAD_HANDLE) before begin
   void carryShared(bool remap_a, bool remap_b, const int64_t n_before[2], SharedStats *shared);
+  bool graftTree(int k, const State &s, double radius, GraftStats &stats, SharedStats *shared,
+                 bool test_edges);
 };
 
 // ---- implementation of the grid_map adapter (fast_terrain_map.cpp:31-91) -------

@@ -22,6 +22,7 @@ using gbp_amd::RRTStarConnectClass;
 using gbp_amd::ReplanSession;
 using gbp_amd::PruneStats;
 using gbp_amd::RerootStats;
+using gbp_amd::GraftStats;
 using gbp_amd::SharedStats;
 namespace planning_utils = gbp_amd::planning_utils;
 using namespace gbp_amd::planning_utils;  // the reference's headers do the same (planning_utils.h)
