@@ -41,6 +41,7 @@ EXPORTS = [
     "gbp_device_free", "gbp_memcpy_h2d", "gbp_memcpy_d2h", "gbp_stream_synchronize",
     "gbp_terrain_create", "gbp_terrain_destroy", "gbp_terrain_info",
     "gbp_terrain_update_dev", "gbp_terrain_update_host", "gbp_terrain_read_host",
+    "gbp_terrain_move_host", "gbp_terrain_move_shift_ms", "gbp_coord_shift",
     "gbp_terrain_set_option", "gbp_terrain_get_option", "gbp_validate_lds_plan",
     "gbp_height_batch_dev", "gbp_height_batch_host",
     "gbp_normal_batch_dev", "gbp_normal_batch_host",
@@ -172,6 +173,9 @@ def load(path=None):
         "gbp_terrain_update_dev": (I, [P, P, I, I64, P, P, P, P, P, P]),
         "gbp_terrain_update_host": (I, [P, P, I, I64, P, P, P, P]),
         "gbp_terrain_read_host": (I, [P, P, I, P]),
+        "gbp_terrain_move_host": (I, [P, I64, I64, P, P, I, I64, P, P, P, P]),
+        "gbp_terrain_move_shift_ms": (I, [P, P]),
+        "gbp_coord_shift": (I, [P, P, I, ctypes.c_double, P]),
         "gbp_terrain_set_option": (I, [P, I, I64]),
         "gbp_terrain_get_option": (I, [P, I, P]),
         "gbp_validate_lds_plan": (I, [I, I, I64, I64, SZ, P, P, P]),

@@ -1171,6 +1171,50 @@ int stage_ws(gbp_terrain *t, F carve) {
 
 }  // namespace
 
+// Everything a handle derives from its coordinate vectors, for gbp_terrain_create
+// and gbp_terrain_move_host alike: bounds, x[nx-2] / y[ny-2], the bracket
+// guess's reciprocal spacings and whether one correction step is exact, the
+// affine fit, the cell-area reciprocal's seed, the device copies d_x / d_y and
+// the mirror's x / y.  t->nx / t->ny are set and do not change, x and y are
+// ascending (coords_ascending: the entries test that first); the current
+// device is t's.  All or nothing: the new device copies are allocated and
+// filled first, and only then are the old ones freed and the fields replaced.
+__attribute__((visibility("hidden"))) int gbp_internal_set_geometry(gbp_terrain *t, const double *x,
+                                                                    const double *y) {
+  const int nx = t->nx, ny = t->ny;
+  double *d_x = nullptr, *d_y = nullptr;
+  auto fail = [&](int code) {
+    if (d_x) (void)hipFree(d_x);
+    if (d_y) (void)hipFree(d_y);
+    return code;
+  };
+  if (hipMalloc((void **)&d_x, sizeof(double) * nx) != hipSuccess) return fail(GBP_E_ALLOC);
+  if (hipMalloc((void **)&d_y, sizeof(double) * ny) != hipSuccess) return fail(GBP_E_ALLOC);
+  if (hipMemcpy(d_x, x, sizeof(double) * nx, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(GBP_E_HIP);
+  if (hipMemcpy(d_y, y, sizeof(double) * ny, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(GBP_E_HIP);
+  if (t->d_x) (void)hipFree(t->d_x);
+  if (t->d_y) (void)hipFree(t->d_y);
+  t->d_x = d_x;
+  t->d_y = d_y;
+  t->bounds[0] = x[0];
+  t->bounds[1] = x[nx - 1];
+  t->bounds[2] = y[0];
+  t->bounds[3] = y[ny - 1];
+  t->xNm = x[nx - 2];
+  t->yNm = y[ny - 2];
+  t->inv_hx = (x[nx - 1] > x[0]) ? (double)(nx - 1) / (x[nx - 1] - x[0]) : 0.0;
+  t->inv_hy = (y[ny - 1] > y[0]) ? (double)(ny - 1) / (y[ny - 1] - y[0]) : 0.0;
+  t->one_x = one_step_exact(x, nx, t->inv_hx);
+  t->one_y = one_step_exact(y, ny, t->inv_hy);
+  t->affine = affine_fit(x, nx, &t->ax, &t->hx, &t->bx) && affine_fit(y, ny, &t->ay, &t->hy, &t->by);
+  t->rcp_seed = verified_rcp_seed(x, nx, y, ny);
+  t->host.x.assign(x, x + nx);
+  t->host.y.assign(y, y + ny);
+  return GBP_OK;
+}
+
 __attribute__((visibility("hidden"))) int gbp_internal_validate_dev_n(
     gbp_terrain *t, int64_t n_max, const int *n_dev, const double *s, const double *a,
     const uint8_t *dir, int dir_all, int adaptive, uint8_t *valid, double *s_new, double *t_new,
@@ -1281,10 +1325,7 @@ int gbp_terrain_create(int device, int nx, int ny, const double *x, const double
   if (nx < 2 || ny < 2) return GBP_E_SHAPE;
   if ((dx == nullptr) != (dy == nullptr) || (dx == nullptr) != (dz == nullptr))
     return GBP_E_INVALID_ARG;
-  for (int i = 0; i + 1 < nx; i++)
-    if (!(x[i] <= x[i + 1])) return GBP_E_INVALID_ARG;  // ascending (fast_terrain_map.cpp:101-108)
-  for (int i = 0; i + 1 < ny; i++)
-    if (!(y[i] <= y[i + 1])) return GBP_E_INVALID_ARG;
+  if (!coords_ascending(x, nx) || !coords_ascending(y, ny)) return GBP_E_INVALID_ARG;
   const size_t cells = (size_t)nx * ny;
   if (storage == GBP_STORAGE_AUTO) {
     storage = GBP_STORAGE_F32;
@@ -1308,22 +1349,8 @@ int gbp_terrain_create(int device, int nx, int ny, const double *x, const double
   t->nx = nx;
   t->ny = ny;
   t->storage = storage;
-  t->bounds[0] = x[0];
-  t->bounds[1] = x[nx - 1];
-  t->bounds[2] = y[0];
-  t->bounds[3] = y[ny - 1];
-  t->xNm = x[nx - 2];
-  t->yNm = y[ny - 2];
-  t->inv_hx = (x[nx - 1] > x[0]) ? (double)(nx - 1) / (x[nx - 1] - x[0]) : 0.0;
-  t->inv_hy = (y[ny - 1] > y[0]) ? (double)(ny - 1) / (y[ny - 1] - y[0]) : 0.0;
-  t->one_x = one_step_exact(x, nx, t->inv_hx);
-  t->one_y = one_step_exact(y, ny, t->inv_hy);
-  t->affine = affine_fit(x, nx, &t->ax, &t->hx, &t->bx) && affine_fit(y, ny, &t->ay, &t->hy, &t->by);
-  t->rcp_seed = verified_rcp_seed(x, nx, y, ny);
   t->host.nx = nx;
   t->host.ny = ny;
-  t->host.x.assign(x, x + nx);
-  t->host.y.assign(y, y + ny);
   t->host.z.resize(cells);
   for (size_t i = 0; i < cells; i++)  // exactly what the device holds
     t->host.z[i] = storage == GBP_STORAGE_F32 ? (double)(float)z[i] : z[i];
@@ -1335,12 +1362,7 @@ int gbp_terrain_create(int device, int nx, int ny, const double *x, const double
     gbp_terrain_destroy(t);
     return code;
   };
-  if (hipMalloc((void **)&t->d_x, sizeof(double) * nx) != hipSuccess) return fail(GBP_E_ALLOC);
-  if (hipMalloc((void **)&t->d_y, sizeof(double) * ny) != hipSuccess) return fail(GBP_E_ALLOC);
-  if (hipMemcpy(t->d_x, x, sizeof(double) * nx, hipMemcpyHostToDevice) != hipSuccess)
-    return fail(GBP_E_HIP);
-  if (hipMemcpy(t->d_y, y, sizeof(double) * ny, hipMemcpyHostToDevice) != hipSuccess)
-    return fail(GBP_E_HIP);
+  if ((rc = gbp_internal_set_geometry(t, x, y))) return fail(rc);
   // heights as x-pairs (gbp_device.h TerrainView)
   const size_t zcount = 2 * ((size_t)nx - 1) * (size_t)ny;
   auto zsrc = [&](size_t k) {
@@ -1379,7 +1401,6 @@ int gbp_terrain_create(int device, int nx, int ny, const double *x, const double
   if (hipStreamCreateWithFlags(&t->host_stream, hipStreamNonBlocking) != hipSuccess)
     return fail(GBP_E_HIP);
   (void)gbp_internal_la_stream(device, t->num_cus);  // ahead of any planner's clock
-  (void)rc;
   *out = t;
   return GBP_OK;
 }

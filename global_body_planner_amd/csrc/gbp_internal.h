@@ -7,7 +7,8 @@
 // gbp_tree_maint.hip: a device tree pruned against a changed terrain,
 // re-rooted at one of its vertices or grafted onto a root state that is none
 // of them; gbp_tree_graft.hip: the graft's connect checks;
-// gbp_terrain.hip: a handle's heights updated in place and its host mirror;
+// gbp_terrain.hip: a handle's heights updated in place, its window moved by
+// whole cells and its host mirror;
 // gbp_replan.hip: RRT*'s kept connections carried between searches and the
 // joined path of two device trees): the handles, the block sizes, the device
 // buffers' carve lists, and a tree's allocations and copies.
@@ -85,6 +86,7 @@ struct gbp_terrain {
     hipEvent_t done;
   };
   std::vector<PendingPatch> pending;
+  float last_shift_ms = -1.0f;      // device time of the last move's shift launch (-1: none)
 };
 
 // brings t->host up to date with the device (gbp_terrain.hip): waits for the
@@ -490,6 +492,22 @@ struct gbp_plan_ws {
 
 // a function one translation unit defines for another: never exported
 #define GBP_INTERNAL __attribute__((visibility("hidden")))
+
+// ascending with no NaN (fast_terrain_map.cpp:101-108), n >= 2: what
+// gbp_terrain_create and gbp_terrain_move_host accept as a coordinate vector
+inline bool coords_ascending(const double *d, int n) {
+  for (int i = 0; i + 1 < n; i++)
+    if (!(d[i] <= d[i + 1])) return false;
+  return true;
+}
+
+// What a handle derives from its coordinate vectors x[t->nx], y[t->ny] (both
+// coords_ascending), in one place for gbp_terrain_create and
+// gbp_terrain_move_host (gbp_engine.hip): bounds, xNm / yNm, inv_h*, one_x /
+// one_y, the affine fit, rcp_seed, the device copies d_x / d_y and the
+// mirror's x / y.  All or nothing: on failure (GBP_E_ALLOC, GBP_E_HIP) the
+// handle is as it was.
+GBP_INTERNAL int gbp_internal_set_geometry(gbp_terrain *t, const double *x, const double *y);
 
 // the device's look-ahead stream of the planner loop (created once per
 // process and device; null on failure); gbp_plan.hip

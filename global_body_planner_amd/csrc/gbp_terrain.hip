@@ -10,6 +10,12 @@
 // that pair the rectangle covers, both in one 2-element store, a single slot
 // at the rectangle's first and last pair row.  No two threads write one
 // address.  The engine-free index rules are host/gbp_terrain_patch.{h,cpp}.
+//
+// gbp_terrain_move_host moves the handle's window by whole cells: the shift
+// kernel copies the overlap from the old x-pairs and slope layers into a second
+// set of buffers (in place, one workgroup would overwrite pairs another has not
+// read yet), the patch kernel writes the uncovered strips behind it on the same
+// stream, and the buffers are swapped once both are through.
 
 #include "gbp_internal.h"
 
@@ -157,19 +163,101 @@ __global__ __launch_bounds__(PATCH_BLOCK) void k_terrain_read(const ZT *zp, doub
   }
 }
 
+// ---- a window moved by whole cells (gbp_terrain_move_host) ---------------------
+struct ShiftArgs {
+  const void *zo;         // the old x-pairs
+  void *zn;               // the new ones: another buffer
+  const double *lo[3];    // the old slope layers [NX][NY] (null: the handle has none)
+  double *ln[3];          // the new ones
+  int NX, NY;
+  int sx, sy;             // new cell (ix, iy) = old cell (ix + sx, iy + sy); |sx| < NX, |sy| < NY
+};
+
+constexpr int SHIFT_ROWS = 4;  // rows per thread and trip: their loads issue before the first store
+
+// Output-centric over the new arrays, lanes along iy, rows by blockIdx.y.
+// blockIdx.z = 0, the heights: new pair (p, iy) = old pair (p + sx, iy + sy),
+// one 2-element load and one 2-element store (8 B a lane for fp32: sy makes
+// the source no better aligned than that; 16 B for fp64).  At the seam rows the
+// old pair row does not exist but one of its cells does: p + sx = -1 takes its
+// slot 1 (old row 0) from slot 0 of old pair 0, p + sx = NX - 1 its slot 0 (old
+// row NX - 1) from slot 1 of old pair NX - 2; the other slot is a strip cell and
+// is the patch launch's, like every pair outside the overlap.
+// blockIdx.z = 1..3, a slope layer: the overlap's cells shifted, every other
+// cell (0, 0, 1), which a patch launch with layers then overwrites.
+template <class ZT>
+__global__ __launch_bounds__(PATCH_BLOCK) void k_terrain_shift(const ShiftArgs A) {
+  using P = typename Pair<ZT>::type;
+  const int iy = (int)(blockIdx.x * PATCH_BLOCK + threadIdx.x);
+  if (iy >= A.NY) return;
+  const int jy = iy + A.sy;
+  const bool col = jy >= 0 && jy < A.NY;
+  const int which = blockIdx.z;
+  if (which == 0) {
+    if (!col) return;
+    const ZT *zo = (const ZT *)A.zo;
+    ZT *zn = (ZT *)A.zn;
+    const int np = A.NX - 1;
+    for (int p0 = (int)blockIdx.y * SHIFT_ROWS; p0 < np; p0 += (int)gridDim.y * SHIFT_ROWS) {
+      P v[SHIFT_ROWS];
+#pragma unroll
+      for (int k = 0; k < SHIFT_ROWS; k++) {
+        const int q = p0 + k + A.sx;
+        if (p0 + k < np && q >= 0 && q < np) v[k] = *(const P *)(zo + 2 * ((int64_t)q * A.NY + jy));
+      }
+#pragma unroll
+      for (int k = 0; k < SHIFT_ROWS; k++) {
+        const int p = p0 + k, q = p + A.sx;
+        if (p >= np) break;
+        ZT *d = zn + 2 * ((int64_t)p * A.NY + iy);
+        if (q >= 0 && q < np)
+          *(P *)d = v[k];
+        else if (q == -1)
+          d[1] = zo[2 * (int64_t)jy];  // old row 0: slot 0 of old pair 0
+        else if (q == np)
+          d[0] = zo[2 * ((int64_t)(np - 1) * A.NY + jy) + 1];  // old row NX - 1: slot 1 of pair NX - 2
+      }
+    }
+  } else {
+    const double *lo = A.lo[which - 1];
+    double *ln = A.ln[which - 1];
+    const double fill = which == 3 ? 1.0 : 0.0;
+    for (int ix = blockIdx.y; ix < A.NX; ix += (int)gridDim.y) {
+      const int jx = ix + A.sx;
+      ln[(int64_t)ix * A.NY + iy] =
+          col && jx >= 0 && jx < A.NX ? lo[(int64_t)jx * A.NY + jy] : fill;
+    }
+  }
+}
+
 bool valid_handle(const gbp_terrain *t) { return t != nullptr && t->d_z != nullptr; }
 
 unsigned rows_grid(int rows) { return (unsigned)std::min(std::max(rows, 1), 65535); }
 
+// the heights and slope layers a launch writes: the handle's own, or the
+// second set a move fills
+struct Dest {
+  void *zp = nullptr;
+  double *lay[3] = {nullptr, nullptr, nullptr};
+};
+Dest dest_of(const gbp_terrain *t) {
+  Dest d;
+  d.zp = t->d_z;
+  d.lay[0] = t->d_dx;
+  d.lay[1] = t->d_dy;
+  d.lay[2] = t->d_dz;
+  return d;
+}
+
 // the apply launch for a checked rectangle and source
-int launch_patch(gbp_terrain *t, const gbp_patch::Rect &q, int layout, int64_t ld, int64_t off,
-                 const void *z, const void *dx, const void *dy, const void *dz,
+int launch_patch(gbp_terrain *t, const Dest &D, const gbp_patch::Rect &q, int layout, int64_t ld,
+                 int64_t off, const void *z, const void *dx, const void *dy, const void *dz,
                  const int32_t *status, hipStream_t st) {
   PatchArgs A;
-  A.zp = t->d_z;
-  A.lay[0] = t->d_dx;
-  A.lay[1] = t->d_dy;
-  A.lay[2] = t->d_dz;
+  A.zp = D.zp;
+  A.lay[0] = D.lay[0];
+  A.lay[1] = D.lay[1];
+  A.lay[2] = D.lay[2];
   A.src[0] = z;
   A.src[1] = dx;
   A.src[2] = dy;
@@ -257,6 +345,35 @@ int stage_rows(void *dst, const void *src, size_t width, size_t spitch, size_t r
   return GBP_OK;
 }
 
+// Host sources of a checked rectangle staged and applied to D on st (not
+// synchronised: buf holds the staged copies until the stream is through).  The
+// rectangle's sub-block of each source array, packed: ld = its own width.
+// GBP_SRC_F64_XMAJOR pointers address the rectangle's first cell.
+int stage_patch(gbp_terrain *t, const Dest &D, const gbp_patch::Rect &q, int src_layout, int64_t ld,
+                const void *z, const void *dx, const void *dy, const void *dz, DevBuf &buf,
+                hipStream_t st) {
+  const bool grid_map = src_layout == GBP_SRC_F32_GRIDMAP;
+  const size_t esz = grid_map ? sizeof(float) : sizeof(double);
+  const size_t cells = (size_t)q.nx * q.ny;
+  const void *hsrc[4] = {z, dx, dy, dz};
+  char *dsrc[4] = {nullptr, nullptr, nullptr, nullptr};
+  const int nsrc = dx ? 4 : 1;
+  int rc = stage_buf(buf, [&](Stage &S) {
+    for (int k = 0; k < nsrc; k++) S.take(dsrc[k], cells * esz);
+  });
+  if (rc) return rc;
+  // GBP_SRC_F32_GRIDMAP: source columns [a0, a0 + q.nx) of rows [b0, b0 + q.ny)
+  const int64_t a0 = t->nx - q.ix0 - q.nx, b0 = t->ny - q.iy0 - q.ny;
+  const int64_t sld = grid_map ? q.nx : q.ny, off = grid_map ? a0 + b0 * sld : 0;
+  for (int k = 0; k < nsrc; k++) {
+    const char *s = (const char *)hsrc[k] + (grid_map ? (size_t)(a0 + b0 * ld) * esz : 0);
+    rc = stage_rows(dsrc[k], s, (size_t)sld * esz, (size_t)ld * esz,
+                    grid_map ? (size_t)q.ny : (size_t)q.nx, st);
+    if (rc) return rc;
+  }
+  return launch_patch(t, D, q, src_layout, sld, off, dsrc[0], dsrc[1], dsrc[2], dsrc[3], nullptr, st);
+}
+
 constexpr size_t MAX_PENDING = 64;  // caller streams with updates the mirror has not taken in
 
 }  // namespace
@@ -298,7 +415,8 @@ int gbp_terrain_update_dev(gbp_terrain *t, const gbp_rect *r, int src_layout, in
         (const double *)z, ld, q.nx, q.ny, status);
     HIPCHK(hipGetLastError());
   }
-  if ((rc = launch_patch(t, q, src_layout, ld, 0, z, dx, dy, dz, need_check ? status : nullptr, st)))
+  if ((rc = launch_patch(t, dest_of(t), q, src_layout, ld, 0, z, dx, dy, dz,
+                         need_check ? status : nullptr, st)))
     return rc;
   // the mirror takes the rectangle in lazily (host_mirror), a rejected one too:
   // its heights are as they were, reading them again changes nothing
@@ -330,34 +448,141 @@ int gbp_terrain_update_host(gbp_terrain *t, const gbp_rect *r, int src_layout, i
   DeviceGuard g(t->device);
   hipStream_t st = t->host_stream;
   if ((rc = wait_pending(t))) return rc;
-  // the rectangle's sub-block of each source array, packed: ld = its own width
-  const bool grid_map = src_layout == GBP_SRC_F32_GRIDMAP;
-  const size_t esz = grid_map ? sizeof(float) : sizeof(double);
-  const size_t cells = (size_t)q.nx * q.ny;
-  const void *hsrc[4] = {z, dx, dy, dz};
-  char *dsrc[4] = {nullptr, nullptr, nullptr, nullptr};
-  const int nsrc = dx ? 4 : 1;
   DevBuf buf;
-  rc = stage_buf(buf, [&](Stage &S) {
-    for (int k = 0; k < nsrc; k++) S.take(dsrc[k], cells * esz);
-  });
-  if (rc) return rc;
-  // GBP_SRC_F32_GRIDMAP: source columns [a0, a0 + q.nx) of rows [b0, b0 + q.ny)
-  const int64_t a0 = t->nx - q.ix0 - q.nx, b0 = t->ny - q.iy0 - q.ny;
-  const int64_t sld = grid_map ? q.nx : q.ny, off = grid_map ? a0 + b0 * sld : 0;
-  for (int k = 0; k < nsrc; k++) {
-    const char *s = (const char *)hsrc[k] + (grid_map ? (size_t)(a0 + b0 * ld) * esz : 0);
-    rc = stage_rows(dsrc[k], s, (size_t)sld * esz, (size_t)ld * esz,
-                    grid_map ? (size_t)q.ny : (size_t)q.nx, st);
-    if (rc) return rc;
-  }
-  if ((rc = launch_patch(t, q, src_layout, sld, off, dsrc[0], dsrc[1], dsrc[2], dsrc[3], nullptr, st)))
-    return rc;
+  if ((rc = stage_patch(t, dest_of(t), q, src_layout, ld, z, dx, dy, dz, buf, st))) return rc;
   HIPCHK(hipStreamSynchronize(st));
   gbp_patch::scatter(t->host.z.data(), t->nx, t->ny, q, src_layout, ld, z,
                      t->storage == GBP_STORAGE_F32);
   t->nan_free = gbp_patch::nan_free_after(t->host.z.data(), t->nx, t->ny, q, t->nan_free != 0);
   return GBP_OK;
+}
+
+int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *x, const double *y,
+                          int src_layout, int64_t ld, const void *z, const void *dx,
+                          const void *dy, const void *dz) {
+  if (!valid_handle(t)) return GBP_E_BAD_HANDLE;
+  if (!x || !y) return GBP_E_INVALID_ARG;
+  const int NX = t->nx, NY = t->ny;
+  gbp_patch::Rect whole;
+  whole.nx = NX;
+  whole.ny = NY;
+  const gbp_patch::MoveRects m = gbp_patch::move_rects(NX, NY, sx, sy);
+  int rc;
+  // the source is read only where there is a strip, and checked only then
+  if (m.nstrips && (rc = gbp_patch::check_source(src_layout, NX, whole, ld, z))) return rc;
+  if ((dx == nullptr) != (dy == nullptr) || (dx == nullptr) != (dz == nullptr))
+    return GBP_E_INVALID_ARG;
+  if (dx && !t->d_dx) return GBP_E_INVALID_ARG;
+  if (!coords_ascending(x, NX) || !coords_ascending(y, NY)) return GBP_E_INVALID_ARG;
+  // all or nothing: the strips are checked before anything is staged
+  const bool f32 = t->storage == GBP_STORAGE_F32;
+  for (int k = 0; f32 && k < m.nstrips; k++)
+    if (!gbp_patch::round_trips(src_layout, NX, NY, m.strip[k], ld,
+                                gbp_patch::move_src(src_layout, ld, z, m.strip[k])))
+      return GBP_E_UNSUPPORTED;
+  DeviceGuard g(t->device);
+  hipStream_t st = t->host_stream;
+  // behind every earlier gbp_terrain_update_dev, whose rectangles the mirror takes in first
+  if ((rc = gbp_internal_mirror_sync(t))) return rc;
+  const bool moved = sx != 0 || sy != 0;
+  // the second set of buffers, freed at scope exit unless the swap took them
+  struct Spare {
+    Dest d;
+    ~Spare() {
+      if (d.zp) (void)hipFree(d.zp);
+      for (double *p : d.lay)
+        if (p) (void)hipFree(p);
+    }
+  } spare;
+  DevBuf staged[2];
+  // device events around the shift launch alone (gbp_terrain_move_shift_ms)
+  struct Timer {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~Timer() {
+      for (hipEvent_t ev : e)
+        if (ev) (void)hipEventDestroy(ev);
+    }
+  } timer;
+  bool timed = false;
+  if (moved) {
+    const size_t cells = (size_t)NX * NY, esz = f32 ? sizeof(float) : sizeof(double);
+    if (hipMalloc(&spare.d.zp, 2 * ((size_t)NX - 1) * NY * esz) != hipSuccess) {
+      spare.d.zp = nullptr;
+      return GBP_E_ALLOC;
+    }
+    for (int k = 0; t->d_dx && k < 3; k++)
+      if (hipMalloc((void **)&spare.d.lay[k], cells * sizeof(double)) != hipSuccess) {
+        spare.d.lay[k] = nullptr;
+        return GBP_E_ALLOC;
+      }
+    if (m.overlap.nx > 0 || t->d_dx) {  // no overlap and no layers: the strip is the whole map
+      ShiftArgs A;
+      A.zo = t->d_z;
+      A.zn = spare.d.zp;
+      const double *lo[3] = {t->d_dx, t->d_dy, t->d_dz};
+      for (int k = 0; k < 3; k++) {
+        A.lo[k] = lo[k];
+        A.ln[k] = spare.d.lay[k];
+      }
+      A.NX = NX;
+      A.NY = NY;
+      // no overlap: every |shift| that large is the same launch (nothing copied, layers filled)
+      A.sx = m.overlap.nx > 0 ? (int)sx : NX;
+      A.sy = m.overlap.nx > 0 ? (int)sy : NY;
+      const dim3 grid((unsigned)((NY + PATCH_BLOCK - 1) / PATCH_BLOCK),
+                      (unsigned)std::min(std::max((NX + SHIFT_ROWS - 1) / SHIFT_ROWS, 1), 4096),
+                      t->d_dx ? 4u : 1u);
+      timed = hipEventCreate(&timer.e[0]) == hipSuccess && hipEventCreate(&timer.e[1]) == hipSuccess &&
+              hipEventRecord(timer.e[0], st) == hipSuccess;
+      if (f32)
+        k_terrain_shift<float><<<grid, PATCH_BLOCK, 0, st>>>(A);
+      else
+        k_terrain_shift<double><<<grid, PATCH_BLOCK, 0, st>>>(A);
+      HIPCHK(hipGetLastError());
+      timed = timed && hipEventRecord(timer.e[1], st) == hipSuccess;
+    }
+    for (int k = 0; k < m.nstrips; k++) {
+      const gbp_patch::Rect &q = m.strip[k];
+      if ((rc = stage_patch(t, spare.d, q, src_layout, ld, gbp_patch::move_src(src_layout, ld, z, q),
+                            gbp_patch::move_src(src_layout, ld, dx, q),
+                            gbp_patch::move_src(src_layout, ld, dy, q),
+                            gbp_patch::move_src(src_layout, ld, dz, q), staged[k], st))) {
+        (void)hipStreamSynchronize(st);  // nothing in flight when the buffers go
+        return rc;
+      }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  float shift_ms = -1.0f;
+  if (timed && hipEventElapsedTime(&shift_ms, timer.e[0], timer.e[1]) != hipSuccess) shift_ms = -1.0f;
+  // the last step that can fail; the rest is the swap and host fields
+  if ((rc = gbp_internal_set_geometry(t, x, y))) return rc;
+  if (moved) {
+    std::swap(t->d_z, spare.d.zp);  // the old buffers leave with `spare`
+    std::swap(t->d_dx, spare.d.lay[0]);
+    std::swap(t->d_dy, spare.d.lay[1]);
+    std::swap(t->d_dz, spare.d.lay[2]);
+    double *mz = t->host.z.data();
+    gbp_patch::shift_mirror(mz, NX, NY, sx, sy, m);
+    for (int k = 0; k < m.nstrips; k++)
+      gbp_patch::scatter(mz, NX, NY, m.strip[k], src_layout, ld,
+                         gbp_patch::move_src(src_layout, ld, z, m.strip[k]), f32);
+    t->nan_free = gbp_patch::nan_free_after_move(mz, NX, NY, m, t->nan_free != 0);
+  }
+  t->last_shift_ms = shift_ms;
+  return GBP_OK;
+}
+
+int gbp_terrain_move_shift_ms(const gbp_terrain *t, float *ms) {
+  if (!valid_handle(t)) return GBP_E_BAD_HANDLE;
+  if (!ms) return GBP_E_INVALID_ARG;
+  *ms = t->last_shift_ms;
+  return GBP_OK;
+}
+
+int gbp_coord_shift(const double *old_c, const double *new_c, int n, double rel_tol, int *shift) {
+  if (!old_c || !new_c || !shift) return 0;
+  return gbp_patch::detect_shift(old_c, new_c, n, rel_tol, shift) ? 1 : 0;
 }
 
 int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z) {

@@ -220,6 +220,15 @@ void FastTerrainMap::updateDataFlat(int ix0, int iy0, int pnx, int pny, const do
       "gbp_terrain_update_host");
 }
 
+void FastTerrainMap::moveDataFlat(int64_t sx, int64_t sy, const double *x, const double *y,
+                                  const double *z, const double *dx, const double *dy,
+                                  const double *dz) {
+  chk(gbp_terrain_move_host(handle_, sx, sy, x, y, GBP_SRC_F64_XMAJOR, y_size_, z, dx, dy, dz),
+      "gbp_terrain_move_host");
+  x_data_.assign(x, x + x_size_);
+  y_data_.assign(y, y + y_size_);
+}
+
 void FastTerrainMap::updateData(const std::vector<std::vector<double>> &z_data,
                                 const std::vector<std::vector<double>> &dx_data,
                                 const std::vector<std::vector<double>> &dy_data,

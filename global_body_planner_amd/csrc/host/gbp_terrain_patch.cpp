@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace gbp_patch {
 
@@ -86,6 +87,77 @@ bool nan_free_after(const double *mirror, int NX, int NY, const Rect &r, bool wa
   if (!was) return nan_free(mirror, (size_t)NX * (size_t)NY);
   for (int ix = r.ix0; ix < r.ix0 + r.nx; ix++)
     if (!nan_free(mirror + (int64_t)ix * NY + r.iy0, (size_t)r.ny)) return false;
+  return true;
+}
+
+MoveRects move_rects(int NX, int NY, int64_t sx, int64_t sy) {
+  MoveRects m;
+  const auto whole = [&] {
+    Rect r;
+    r.nx = NX;
+    r.ny = NY;
+    return r;
+  };
+  if (sx <= -(int64_t)NX || sx >= NX || sy <= -(int64_t)NY || sy >= NY) {
+    m.nstrips = 1;
+    m.strip[0] = whole();
+    return m;
+  }
+  const int ax = (int)(sx < 0 ? -sx : sx), ay = (int)(sy < 0 ? -sy : sy);
+  Rect &o = m.overlap;
+  o.ix0 = sx < 0 ? ax : 0;
+  o.iy0 = sy < 0 ? ay : 0;
+  o.nx = NX - ax;
+  o.ny = NY - ay;
+  if (ax) {  // |sx| full rows: below the overlap for sx < 0, above it otherwise
+    Rect &r = m.strip[m.nstrips++];
+    r.ix0 = sx < 0 ? 0 : o.nx;
+    r.iy0 = 0;
+    r.nx = ax;
+    r.ny = NY;
+  }
+  if (ay) {  // |sy| columns of the overlap's rows
+    Rect &r = m.strip[m.nstrips++];
+    r.ix0 = o.ix0;
+    r.iy0 = sy < 0 ? 0 : o.ny;
+    r.nx = o.nx;
+    r.ny = ay;
+  }
+  return m;
+}
+
+void shift_mirror(double *mirror, int NX, int NY, int64_t sx, int64_t sy, const MoveRects &m) {
+  const Rect &o = m.overlap;
+  if (o.nx <= 0 || o.ny <= 0 || (sx == 0 && sy == 0)) return;
+  // sx > 0 reads rows above the ones it writes: ascending; sx < 0 descending;
+  // within a row (sx = 0) memmove takes the overlap of source and destination
+  for (int k = 0; k < o.nx; k++) {
+    const int ix = sx >= 0 ? o.ix0 + k : o.ix0 + o.nx - 1 - k;
+    std::memmove(mirror + (int64_t)ix * NY + o.iy0, mirror + (int64_t)(ix + sx) * NY + (o.iy0 + sy),
+                 sizeof(double) * (size_t)o.ny);
+  }
+}
+
+bool nan_free_after_move(const double *mirror, int NX, int NY, const MoveRects &m, bool was) {
+  if (!was) return nan_free(mirror, (size_t)NX * (size_t)NY);
+  for (int k = 0; k < m.nstrips; k++)
+    if (!nan_free_after(mirror, NX, NY, m.strip[k], true)) return false;
+  return true;
+}
+
+bool detect_shift(const double *o, const double *n, int N, double rel_tol, int *shift) {
+  if (N < 2) return false;
+  const double h = (o[N - 1] - o[0]) / (double)(N - 1);
+  if (!(h > 0) || !std::isfinite(h)) return false;
+  const double s = std::round((n[0] - o[0]) / h);
+  if (!(std::fabs(s) < 2147483647.0)) return false;  // NaN as well
+  const int64_t sh = (int64_t)s;
+  const double tol = h * rel_tol;
+  for (int64_t i = std::max<int64_t>(0, -sh); i < std::min<int64_t>(N, (int64_t)N - sh); i++)
+    if (!(std::fabs(n[i] - o[i + sh]) <= tol)) return false;
+  for (int i = 0; i < N; i++)
+    if (std::isnan(n[i])) return false;
+  *shift = (int)sh;
   return true;
 }
 

@@ -2,8 +2,12 @@
 // (gbp_terrain_update_*, gbp_terrain_read_host; internal to libgbp): the
 // rectangle and its pair rows, where a cell lies in either source layout, the
 // float round-trip check of a patch and the scatter into the handle's host
-// mirror.  No HIP here: csrc/gbp_terrain.hip runs the same index rules on the
-// device, and tests/native/terrain_patch_probe.cpp runs these under sanitizers.
+// mirror; and of a window moved by whole cells (gbp_terrain_move_host): its
+// overlap and strips, the mirror's shift, nan_free after it and the detection
+// of a whole-cell shift between two coordinate vectors.  No HIP here:
+// csrc/gbp_terrain.hip runs the same index rules on the device, and
+// tests/native/terrain_patch_probe.cpp and terrain_move_probe.cpp run these
+// under sanitizers.
 #pragma once
 
 #include <cstddef>
@@ -75,5 +79,46 @@ bool nan_free(const double *z, size_t n);
 // whole mirror is scanned (a NaN written clears it; the values written may
 // have replaced the last NaN).
 bool nan_free_after(const double *mirror, int NX, int NY, const Rect &r, bool was);
+
+// ---- a window moved by whole cells (gbp_terrain_move_host) --------------------
+// New cell (ix, iy) holds what old cell (ix + sx, iy + sy) held where that cell
+// lies in the old map: the overlap, in new indices.  The other new cells are
+// the strips, an L of at most two rectangles: |sx| full rows, then |sy|
+// columns of the rows that are left.  Overlap and strips partition the map.
+// |sx| >= NX or |sy| >= NY: no overlap (overlap.nx = overlap.ny = 0) and one
+// strip, the whole map; sx = sy = 0: no strip.
+struct MoveRects {
+  Rect overlap;
+  int nstrips = 0;
+  Rect strip[2];
+};
+MoveRects move_rects(int NX, int NY, int64_t sx, int64_t sy);
+
+// a strip's cells in a source that holds the whole new map: the pointer a
+// Rect-relative GBP_SRC_F64_XMAJOR index (src_index) starts from; a
+// GBP_SRC_F32_GRIDMAP layer is indexed by the map's own cell, so it is src
+inline const void *move_src(int layout, int64_t ld, const void *src, const Rect &r) {
+  return layout == GBP_SRC_F32_GRIDMAP || !src
+             ? src
+             : (const void *)((const double *)src + (int64_t)r.ix0 * ld + r.iy0);
+}
+
+// the mirror's overlap shifted in place: mirror[ix][iy] = old mirror[ix + sx]
+// [iy + sy] over m.overlap, rows in the order in which no row is read after it
+// was written, each row by memmove; the strips' cells keep stale values
+void shift_mirror(double *mirror, int NX, int NY, int64_t sx, int64_t sy, const MoveRects &m);
+
+// nan_free once the strips have been scattered behind shift_mirror: kept when
+// it held before and no strip cell is NaN (the overlap's cells all come from
+// the old map), otherwise one full scan
+bool nan_free_after_move(const double *mirror, int NX, int NY, const MoveRects &m, bool was);
+
+// Is the coordinate vector n[0, N) the vector o[0, N) displaced by a whole
+// number of cells?  h = (o[N-1] - o[0]) / (N - 1), *shift = round((n[0] - o[0])
+// / h); accepted when every new position with an old counterpart, n[i] against
+// o[i + shift], lies within h * rel_tol of it (with |shift| >= N there is no
+// counterpart and no height is reused: accepted).  false for N < 2, h not
+// positive and finite, a NaN position, or a shift that does not fit an int.
+bool detect_shift(const double *o, const double *n, int N, double rel_tol, int *shift);
 
 }  // namespace gbp_patch

@@ -157,6 +157,40 @@ class Terrain:
                                                 *[_np_ptr(v) for v in arrs]), "update")
         return None
 
+    def move(self, sx, sy, x, y, z, dx=None, dy=None, dz=None, layout=L.SRC_F64_XMAJOR):
+        """Move the window by (sx, sy) whole cells in place
+        (gbp_terrain_move_host): x, y are the new coordinate vectors (the
+        handle's sizes), new cell (ix, iy) keeps what old cell (ix + sx, iy +
+        sy) held where the old map has it, and every other cell is read from
+        z (and dx / dy / dz, all three or none), the WHOLE new map: float64
+        [NX][ld >= NY] for SRC_F64_XMAJOR, a float32 grid_map layer [NY][ld >=
+        NX] for SRC_F32_GRIDMAP (as `update`).  Only those cells are read.
+        Options, sampling, workspaces and PlanWorkspace objects of the handle
+        stay; afterwards it equals a fresh Terrain of the moved arrays.  numpy
+        input, synchronous; a refused move (GbpError: E_UNSUPPORTED for a new
+        height an fp32 handle cannot hold, E_INVALID_ARG for descending
+        coordinates) changes nothing.
+
+        A planner.ReplanSession on this terrain goes on across a move:
+        T.move(...) and then session.map_changed(), which prunes what the new
+        window no longer holds (see planner.ReplanSession.map_changed)."""
+        x = np.ascontiguousarray(_np(x), np.float64)
+        y = np.ascontiguousarray(_np(y), np.float64)
+        if x.shape != (self.nx,) or y.shape != (self.ny,):
+            raise ValueError(f"x, y must have the handle's sizes ({self.nx}, {self.ny})")
+        dt = np.float32 if layout == L.SRC_F32_GRIDMAP else np.float64
+        arrs = [None if v is None else np.ascontiguousarray(_np(v), dt) for v in (z, dx, dy, dz)]
+        ld = 0
+        if arrs[0] is not None:
+            rows = self.ny if layout == L.SRC_F32_GRIDMAP else self.nx
+            if arrs[0].ndim != 2 or arrs[0].shape[0] != rows or \
+                    any(v is not None and v.shape != arrs[0].shape for v in arrs[1:]):
+                raise ValueError(f"z, dx, dy, dz must be whole maps of one shape [{rows}][ld]")
+            ld = int(arrs[0].shape[1])
+        check(self._lib.gbp_terrain_move_host(self._h, int(sx), int(sy), _np_ptr(x), _np_ptr(y),
+                                              int(layout), ld, *[_np_ptr(v) for v in arrs]),
+              "move")
+
     def read(self, rect=None, copy=0):
         """The heights the device holds (gbp_terrain_read_host), float64
         [nx][ny] of rect = (ix0, iy0, nx, ny), the whole map when None.  A

@@ -609,7 +609,18 @@ class ReplanSession:
     def map_changed(self):
         """The terrain was updated in place: both trees pruned where they are,
         the list carried through the prunes' device remaps and ranked again.
-        Returns (prune stats of tree a and b, shared stats)."""
+        Returns (prune stats of tree a and b, shared stats).
+
+        A moved window (engine.Terrain.move) is such an update: the handle is
+        the same one, so the session goes on,
+
+            T.move(sx, sy, x_new, y_new, z_new)   # the map scrolled by whole cells
+            session.map_changed()                 # prune what left the window
+            session.search(...)
+
+        A vertex whose edge now leaves the window reads GBP_F_OOD, is invalid
+        and is pruned like any other; the roots are never tested, so keeping
+        both inside the new window is the caller's."""
         self._need()
         before = list(self.known)
         stats = []

@@ -134,7 +134,8 @@ int gbp_terrain_info(const gbp_terrain *t, int *nx, int *ny, int *storage,
  * the gbp_plan_ws objects created for the handle are untouched: afterwards the
  * handle is bit for bit what gbp_terrain_create would have made of the patched
  * map with the same storage and options.  An update never changes the storage
- * type: a changed geometry or storage stays a new gbp_terrain_create. */
+ * type: a changed size or storage type stays a new gbp_terrain_create (a window
+ * of the same size moved by whole cells is gbp_terrain_move_host, below). */
 typedef struct gbp_rect { int32_t ix0, iy0, nx, ny; } gbp_rect; /* cells [ix0, ix0+nx) x [iy0, iy0+ny); NULL = whole map */
 #define GBP_SRC_F64_XMAJOR  0  /* double src[i*ld + j] = z[ix0+i][iy0+j], ld >= rect.ny */
 #define GBP_SRC_F32_GRIDMAP 1  /* a whole grid_map layer as it lies in memory: float,
@@ -175,6 +176,67 @@ int gbp_terrain_update_host(gbp_terrain *t, const gbp_rect *r, int src_layout, i
  * of pair ix (row nx-1, which has none, from slot 1 of pair nx-2), copy 1 reads
  * row ix from slot 1 of pair ix-1 (row 0 from slot 0 of pair 0). */
 int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z);
+
+/* ---- a terrain's window moved by whole cells --------------------------------
+ * A robot-centred elevation map scrolls by whole cells as the robot moves
+ * (grid_map's move): the map keeps its size, its coordinates are displaced and
+ * only a strip of its heights is new.  gbp_terrain_move_host gives a living
+ * handle that new geometry: x[nx], y[ny] are the new coordinate vectors (the
+ * handle's sizes, ascending as at create), and new cell (ix, iy) holds what old
+ * cell (ix + sx, iy + sy) held where that cell lies in the old map (the
+ * overlap, shifted on the device).  Every other new cell (the strips: |sx| full
+ * rows and |sy| columns of the remaining rows) takes its height, and when dx /
+ * dy / dz are given its slope values, from the source, which is the WHOLE new
+ * map in src_layout: GBP_SRC_F64_XMAJOR z[ix*ld + iy] with ld >= ny,
+ * GBP_SRC_F32_GRIDMAP as above.  Only the strips' cells are read and staged; a
+ * value in the overlap's part of the source is never looked at.
+ * The shift is the caller's statement: the old and new coordinates are not
+ * compared (grid_map recomputes positions from the new centre, and they may
+ * differ from the displaced old ones in the last ulp).  |sx| >= nx or |sy| >=
+ * ny leaves no overlap: the whole map comes from the source.  sx = sy = 0 only
+ * replaces the coordinate vectors (z may then be NULL).
+ * Afterwards the handle is bit for bit what gbp_terrain_create makes of x, y
+ * and the moved arrays with the same storage and options: heights in both
+ * copies of every x-pair, slope layers, bounds, everything derived from the
+ * coordinates (the coordinate class may change, e.g. affine to not affine, and
+ * GBP_OPT_COORD_MODE with it), the host copy and GBP_OPT_NAN_FREE.  Options,
+ * sampling, workspaces and the gbp_plan_ws objects of the handle stay.
+ * Slope layers given to a handle created without them: GBP_E_INVALID_ARG.
+ * Omitted for a handle that has them: the overlap's slope values shift with the
+ * heights and the strips' slope cells become (0, 0, 1), what a create without
+ * layers reads everywhere.
+ * All or nothing: descending coordinates or a NaN among them:
+ * GBP_E_INVALID_ARG; an ld below the layout's minimum: GBP_E_SHAPE; an
+ * fp32-storage handle and a strip height that is neither NaN nor
+ * float-representable: GBP_E_UNSUPPORTED, found on the host before anything is
+ * staged.  The moved map is built in a second set of device buffers, which
+ * replace the handle's own as the last step together with the host-side fields,
+ * so a failure at any point leaves the handle as it was.  The old buffers are
+ * then freed: between moves the handle holds one copy of the map.
+ * Ordering: as gbp_terrain_update_host.  The entry runs on the handle's host
+ * stream behind every earlier gbp_terrain_update_dev, whose rectangles the host
+ * copy takes in first, and returns when the device and the host copy hold the
+ * moved map.  Work of the caller's on other streams that reads the handle must
+ * have finished.  There is no _dev form: a launch's view of the terrain (the
+ * buffers, the bounds and the other coordinate-derived scalars) is built from
+ * host fields when the launch is enqueued, so a move ordered on a caller's
+ * stream would need another design. */
+int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *x,
+                          const double *y, int src_layout, int64_t ld, const void *z,
+                          const void *dx, const void *dy, const void *dz);
+/* Device time (ms, by events on the handle's host stream) of the shift launch of
+ * the last gbp_terrain_move_host that succeeded; -1 when there was none or it
+ * launched none (sx = sy = 0, or no overlap and no slope layers).  For
+ * tools/terrain_move_ab.py. */
+int gbp_terrain_move_shift_ms(const gbp_terrain *t, float *ms);
+/* Is the coordinate vector new_c[n] the vector old_c[n] displaced by a whole
+ * number of cells (no device call)?  h = (old_c[n-1] - old_c[0]) / (n - 1),
+ * *shift = round((new_c[0] - old_c[0]) / h); returns 1 when every new position
+ * with an old counterpart, new_c[i] against old_c[i + *shift], lies within
+ * h * rel_tol of it (none has one when |*shift| >= n: 1), else 0 with *shift
+ * untouched: a changed spacing, a displacement by a fraction of a cell, n < 2,
+ * NaN.  FastTerrainMap::moveFromGridMap calls it with rel_tol = 1.0 / 1024. */
+int gbp_coord_shift(const double *old_c, const double *new_c, int n, double rel_tol, int *shift);
 
 /* engine options (per handle) */
 #define GBP_OPT_KERNEL        1  /* GBP_KERNEL_* for the validate/extend entry points */

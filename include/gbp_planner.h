@@ -154,6 +154,29 @@ class FastTerrainMap {
   template <class GridMap>
   bool updateFromGridMap(const GridMap &map);
 
+  // The loaded map's window moved by (sx, sy) whole cells, in place
+  // (gbp_terrain_move_host): new cell (i, j) keeps what old cell (i + sx, j +
+  // sy) held where the old map has that cell, every other cell is read from
+  // z (and dx / dy / dz: all three or null), the WHOLE new map, flat x-major
+  // z[i * y_size + j]; x[x_size], y[y_size] are the new coordinates.  The
+  // handle, its options, sampling and workspaces and the planner workspaces
+  // created for it stay, and so may a ReplanSession: mapChanged after the move
+  // prunes what the new window no longer holds.  Null slope layers for a map
+  // loaded with them: the kept cells' slopes move along, the new cells read
+  // (0, 0, 1).
+  void moveDataFlat(int64_t sx, int64_t sy, const double *x, const double *y, const double *z,
+                    const double *dx, const double *dy, const double *dz);
+  // terrainMapCallback on a robot-centred map that scrolls by whole cells
+  // (grid_map's move; start index 0 as loadDataFromGridMap).  The map's size
+  // and the presence of slope layers must equal the loaded map's, and with
+  // sx = round((x_new[0] - x_old[0]) / h), h = (x_old[nx-1] - x_old[0]) / (nx -
+  // 1) (sy likewise) every new position that has an old counterpart must lie
+  // within h / 1024 of it (gbp_coord_shift): then moveDataFlat(sx, sy, ...)
+  // and true.  Otherwise (another size, a changed spacing, a displacement by a
+  // fraction of a cell) loadDataFromGridMap(map) and false.
+  template <class GridMap>
+  bool moveFromGridMap(const GridMap &map);
+
   double getGroundHeight(const double x, const double y);               // :94-132
   bool heightIsNan(const double x, const double y);                     // :135-157
   std::array<double, 3> getSurfaceNormal(const double x, const double y);  // :160-213
@@ -785,7 +808,12 @@ struct SharedStats {
 //              the trees, list and best of buildRRTStarConnectDevice with the
 //              same arguments.  Returns whether a connection is held.
 //   mapChanged the terrain handle was updated in place (updateData /
-//              updateDataFlat): both trees are pruned where they are and the
+//              updateDataFlat) or its window moved (moveDataFlat /
+//              moveFromGridMap: the handle is the same one, so the session
+//              goes on; a vertex whose edge now leaves the window is
+//              GBP_F_OOD, hence invalid, hence pruned like any other, and the
+//              roots are never tested: keeping them inside the window is the
+//              caller's): both trees are pruned where they are and the
 //              list is carried through the prunes' device remaps and ranked
 //              again.  Neither the remaps nor the list come to the host; the
 //              prune's own read-back (the edges' decisions and flags, for
@@ -952,6 +980,61 @@ bool FastTerrainMap::updateFromGridMap(const GridMap &map) {
     }
   updateDataFlat(0, 0, x_size, y_size, z.data(), slopes ? dx.data() : nullptr,
                  slopes ? dy.data() : nullptr, slopes ? dz.data() : nullptr);
+  return true;
+}
+
+template <class GridMap>
+bool FastTerrainMap::moveFromGridMap(const GridMap &map) {
+  using Index = typename std::decay<decltype(map.getStartIndex())>::type;
+  using Position = typename std::decay<decltype(map.getPosition())>::type;
+  const int x_size = map.getSize()(0);
+  const int y_size = map.getSize()(1);
+  const bool slopes = map.exists("dx");
+  bool same = handle_ && owned_ && x_size == x_size_ && y_size == y_size_ && slopes == slopes_ &&
+              x_data_.size() == (size_t)x_size && y_data_.size() == (size_t)y_size;
+  std::vector<double> x, y;
+  int sx = 0, sy = 0;
+  if (same) {
+    x.resize(x_size);
+    y.resize(y_size);
+    for (int i = 0; i < x_size; i++) {
+      Index index((x_size - 1) - i, 0);
+      Position position;
+      map.getPosition(index, position);
+      x[i] = position.x();
+    }
+    for (int i = 0; i < y_size; i++) {
+      Index index(0, (y_size - 1) - i);
+      Position position;
+      map.getPosition(index, position);
+      y[i] = position.y();
+    }
+    same = gbp_coord_shift(x_data_.data(), x.data(), x_size, 1.0 / 1024, &sx) &&
+           gbp_coord_shift(y_data_.data(), y.data(), y_size, 1.0 / 1024, &sy);
+  }
+  if (!same) {
+    loadDataFromGridMap(map);
+    return false;
+  }
+  std::vector<double> z((size_t)x_size * y_size), dx, dy, dz;
+  if (slopes) {
+    dx.resize(z.size());
+    dy.resize(z.size());
+    dz.resize(z.size());
+  }
+  for (int i = 0; i < x_size; i++)
+    for (int j = 0; j < y_size; j++) {
+      Index index((x_size - 1) - i, (y_size - 1) - j);
+      const size_t k = (size_t)i * y_size + j;
+      z[k] = (double)map.at("elevation", index);
+      if (slopes) {
+        dx[k] = (double)map.at("dx", index);
+        dy[k] = (double)map.at("dy", index);
+        dz[k] = (double)map.at("dz", index);
+      }
+    }
+  moveDataFlat(sx, sy, x.data(), y.data(), z.data(), slopes ? dx.data() : nullptr,
+               slopes ? dy.data() : nullptr, slopes ? dz.data() : nullptr);
   return true;
 }
 
