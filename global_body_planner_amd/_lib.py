@@ -73,6 +73,7 @@ EXPORTS = [
     "gbp_tree_revalidate_keep_host", "gbp_tree_reroot_keep_host",
     "gbp_tree_graft_check_dev", "gbp_tree_graft_dev", "gbp_tree_graft_last",
     "gbp_tree_graft_host", "gbp_tree_graft_keep_host",
+    "gbp_tree_trim_flags_dev", "gbp_tree_trim_host", "gbp_tree_trim_keep_host",
 ]
 
 
@@ -110,6 +111,14 @@ class GraftStats(ctypes.Structure):
                 ("n_attached", ctypes.c_int64), ("n_outside", ctypes.c_int64),
                 ("n_edge_invalid", ctypes.c_int64), ("n_inherited", ctypes.c_int64),
                 ("depth", ctypes.c_int64)]
+
+
+class TrimStats(ctypes.Structure):
+    """gbp_trim_stats (include/gbp.h): what a trim by cost dropped and why."""
+    _fields_ = [("n_before", ctypes.c_int64), ("n_kept", ctypes.c_int64),
+                ("n_over_bound", ctypes.c_int64), ("n_over_budget", ctypes.c_int64),
+                ("n_protected", ctypes.c_int64), ("n_inherited", ctypes.c_int64),
+                ("error", ctypes.c_int64), ("cut", ctypes.c_double)]
 
 
 class SharedStats(ctypes.Structure):
@@ -230,6 +239,9 @@ def load(path=None):
         "gbp_tree_graft_last": (I, [P, P]),
         "gbp_tree_graft_host": (I, [P, P, P, ctypes.c_double, I, I, I, P, P, P]),
         "gbp_tree_graft_keep_host": (I, [P, P, P, ctypes.c_double, I, I, I, P, P, I64, P, P]),
+        "gbp_tree_trim_flags_dev": (I, [P, P, I64, ctypes.c_double, I64, ctypes.c_int32, P, P, P, P]),
+        "gbp_tree_trim_host": (I, [P, P, ctypes.c_double, I64, ctypes.c_int32, P, P, P]),
+        "gbp_tree_trim_keep_host": (I, [P, P, ctypes.c_double, I64, ctypes.c_int32, P, P, I64, P, P]),
         "gbp_plan_ws_create": (I, [P, I64, P]),
         "gbp_plan_ws_destroy": (I, [P]),
         "gbp_plan_reset": (I, [P, I64, P]),

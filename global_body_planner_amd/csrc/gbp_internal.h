@@ -7,6 +7,7 @@
 // gbp_tree_maint.hip: a device tree pruned against a changed terrain,
 // re-rooted at one of its vertices or grafted onto a root state that is none
 // of them; gbp_tree_graft.hip: the graft's connect checks;
+// gbp_tree_trim.hip: a device tree's trim flags by best cost or vertex budget;
 // gbp_terrain.hip: a handle's heights updated in place, its window moved by
 // whole cells and its host mirror;
 // gbp_replan.hip: RRT*'s kept connections carried between searches and the
@@ -250,7 +251,8 @@ struct gbp_tree {
   int32_t *prev = nullptr;    // [cap] previous sibling (-1: first child): O(1) removeEdge
   int32_t *bfs = nullptr;     // [2 cap] scratch: the subtree update's two level queues
   int32_t *count = nullptr;   // [1] number of vertices (device resident)
-  // gbp_tree_revalidate_dev's attempt rows (grow-only; kernels do not read these two)
+  // gbp_tree_revalidate_dev's attempt rows, gbp_tree_trim_flags_dev's f and counts
+  // (grow-only; a kernel gets pointers carved from it, never these two)
   void *rv = nullptr;
   size_t rv_bytes = 0;
 };

@@ -2328,6 +2328,11 @@ bool ReplanSession::search(double max_time, int64_t max_halves, BatchStats *stat
       cost_vector_times_.push_back(clk.seconds());
     }
     S.group = std::min(S.group * 2, S.g_max);
+    // the tree limit, once per group (setTreeLimit)
+    if (tree_limit_ > 0 && (S.known[0] > tree_limit_ || S.known[1] > tree_limit_)) {
+      trim(tree_trim_to_, nullptr);
+      trims_by_search_++;
+    }
   }
   extend_counter_ = ps.ext_counter;
   rewires_ = ps.stat_rewires;
@@ -2406,6 +2411,46 @@ void ReplanSession::mapChanged(FastTerrainMap &terrain, PruneStats stats[2], Sha
     done.n_inherited = ps.n_inherited;
     S.known[k] = ps.n_kept;
     if (stats) stats[k] = done;
+  }
+  carryShared(true, true, before, shared);
+}
+
+void ReplanSession::setTreeLimit(int64_t max_vertices, int64_t trim_to) {
+  if (max_vertices < 0 || (max_vertices > 0 && (trim_to < 1 || trim_to > max_vertices)))
+    throw EngineError(GBP_E_INVALID_ARG, "ReplanSession: a tree limit needs 1 <= trim_to <= max_vertices");
+  tree_limit_ = max_vertices;
+  tree_trim_to_ = max_vertices > 0 ? trim_to : 0;
+}
+
+// both trees trimmed on the session's own stream (no terrain is involved), the
+// best connection's vertices protected, then the list as after a map change
+void ReplanSession::trim(int64_t max_vertices, TrimStats stats[2], SharedStats *shared) {
+  Impl &I = impl();
+  DeviceSearch &S = I.S;
+  if (max_vertices < 0) throw EngineError(GBP_E_INVALID_ARG, "ReplanSession: a negative vertex budget");
+  const int64_t before[2] = {S.known[0], S.known[1]};
+  const bool held = S.ps.best_a >= 0 && S.ps.best_b >= 0;
+  const double bound = held ? S.ps.best_cost : std::numeric_limits<double>::infinity();
+  const int32_t protect[2] = {held ? S.ps.best_a : -1, held ? S.ps.best_b : -1};
+  for (int k = 0; k < 2; k++)
+    I.remap[k].reserve(I.device, before[k], sizeof(int32_t), 1 << 12, "ReplanSession: remap");
+  for (int k = 0; k < 2; k++) {
+    gbp_trim_stats ts{};
+    chk(gbp_tree_trim_keep_host(S.tree[k], S.tree[k ^ 1], bound, max_vertices, protect[k], nullptr,
+                                I.remap[k].data<int32_t>(), I.remap[k].capacity(), &ts, S.stream),
+        "ReplanSession: trim");
+    S.known[k] = ts.n_kept;
+    if (stats) {
+      TrimStats done;
+      done.n_before = ts.n_before;
+      done.n_kept = ts.n_kept;
+      done.n_over_bound = ts.n_over_bound;
+      done.n_over_budget = ts.n_over_budget;
+      done.n_protected = ts.n_protected;
+      done.n_inherited = ts.n_inherited;
+      done.cut = ts.cut;
+      stats[k] = done;
+    }
   }
   carryShared(true, true, before, shared);
 }

@@ -43,6 +43,29 @@ bool applyPruneRemap(const std::vector<int32_t> &remap, TreeDump &trees, int k) 
   return true;
 }
 
+bool applyTrimRemap(const std::vector<int32_t> &remap, const std::vector<uint8_t> &keep, TreeDump &trees,
+                    int k, TrimRemapRecord *rec) {
+  const size_t n = remap.size();
+  if (k < 0 || k > 1 || n < 1 || keep.size() != n || trees.parent[k].size() != n || !keep[0]) return false;
+  const std::vector<int32_t> &parent = trees.parent[k];
+  TrimRemapRecord r;
+  r.n_before = (int64_t)n;
+  for (size_t i = 0; i < n; i++) {
+    if (remap[i] >= 0) {
+      if (!keep[i]) return false;
+      r.n_kept++;
+    } else if (!keep[i]) {
+      r.n_flagged++;
+    } else {  // dropped with its flag set: only below a dropped parent
+      if (i == 0 || parent[i] < 0 || (size_t)parent[i] >= n || remap[parent[i]] >= 0) return false;
+      r.n_inherited++;
+    }
+  }
+  if (!applyPruneRemap(remap, trees, k)) return false;
+  if (rec) *rec = r;
+  return true;
+}
+
 int64_t applyRerootRemap(const int32_t *remap, int64_t n, int32_t new_root, State *v, Action *a,
                          int32_t *parent, double *g) {
   if (n < 1 || !remap || !v || !a || !parent || new_root < 0 || new_root >= n || remap[new_root] != 0)

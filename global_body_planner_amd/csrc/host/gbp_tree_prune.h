@@ -22,6 +22,24 @@ int64_t applyPruneRemap(const int32_t *remap, int64_t n, State *v, Action *a, in
 // tree k of a TreeDump (its four vectors shortened to the survivors)
 bool applyPruneRemap(const std::vector<int32_t> &remap, TreeDump &trees, int k);
 
+// What a trim by cost (gbp_tree_trim_host, include/gbp.h) did to a tree, counted
+// from its remap and stage A's flags alone.
+struct TrimRemapRecord {
+  int64_t n_before = 0;     // vertices before the trim
+  int64_t n_kept = 0;       // ... and after it
+  int64_t n_flagged = 0;    // dropped: their own flag is 0 (over the bound or the budget)
+  int64_t n_inherited = 0;  // dropped though their own flag is 1: an ancestor's is 0
+};
+
+// remap[n] as the device trim returns it (a prune's remap, see above) and
+// keep[n], stage A's flags (gbp_tree_trim_flags_dev): a kept vertex has keep !=
+// 0 and keep[0] != 0.  Tree k of `trees` is shortened to the survivors as
+// applyPruneRemap does, g's rows moved as they are (a trim changes no g), and
+// *rec (may be null) filled.  False, with nothing changed, when remap is no such
+// map for these parents or keeps a vertex against its flag.
+bool applyTrimRemap(const std::vector<int32_t> &remap, const std::vector<uint8_t> &keep, TreeDump &trees,
+                    int k, TrimRemapRecord *rec = nullptr);
+
 // remap[n] as the device re-root returns it: new_root numbered 0, the other
 // kept vertices 1, 2, ... in ascending old index, a kept vertex other than
 // new_root under a kept parent.  Moves the kept rows to the front in place:

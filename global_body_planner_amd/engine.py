@@ -613,6 +613,47 @@ class DeviceTree:
         stats["n_resolved"] = k.value
         return remap, stats
 
+    def trim(self, other, bound=float("inf"), max_keep=0, protect=-1, remap_dev=None):
+        """gbp_tree_trim_host: drops vertices by f = g + poseDistance(v, root of
+        `other`), in HBM, on torch's current stream.  A vertex goes when
+        f > bound (the held best cost; inf or NaN: no bound) or, with
+        1 <= max_keep < len(self), when it is not among the max_keep - 1
+        non-root vertices of least f (a group of equal f at the cut goes
+        whole); vertex `protect` and its ancestors stay whatever their f
+        (-1: none); a vertex below a dropped one goes with it.  The kept
+        vertices keep their order and their g, as after revalidate.  Returns
+        (remap, stats): remap [n before] int32, a vertex's new index or -1;
+        stats a dict of n_before, n_kept, n_over_bound, n_over_budget (not
+        over the bound), n_protected (failed a test, kept by protection),
+        n_inherited (dropped through an ancestor only), error and cut.
+        remap_dev: as in revalidate (gbp_tree_trim_keep_host)."""
+        remap = np.empty(len(self), np.int32)
+        st = L.TrimStats()
+        args = (self._h, other._h, float(bound), int(max_keep), int(protect), _np_ptr(remap))
+        if remap_dev is not None:
+            check(self._lib.gbp_tree_trim_keep_host(*args, _ptr(remap_dev), remap_dev.numel(),
+                                                    ctypes.byref(st), _stream(self.device)),
+                  "tree_trim_keep")
+        else:
+            check(self._lib.gbp_tree_trim_host(*args, ctypes.byref(st), _stream(self.device)),
+                  "tree_trim")
+        return remap, {name: getattr(st, name) for name, _ in L.TrimStats._fields_}
+
+    def trim_flags(self, other, bound=float("inf"), max_keep=0, protect=-1, n=None):
+        """gbp_tree_trim_flags_dev, the trim's stage A, on torch's current
+        stream: (keep uint8 [n], f float64 [n], stats int64 [8]) device tensors
+        (stats in gbp_trim_stats' layout, its last word the bits of cut); keep
+        is what gbp_tree_prune_dev takes as edge_valid."""
+        n = len(self) if n is None else int(n)
+        dev = torch.device("cuda", self.device)
+        keep = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+        f = torch.zeros(n, dtype=torch.float64, device=dev)
+        st = torch.zeros(len(L.TrimStats._fields_), dtype=torch.int64, device=dev)
+        check(self._lib.gbp_tree_trim_flags_dev(self._h, other._h, n, float(bound), int(max_keep),
+                                                int(protect), _ptr(keep), _ptr(f), _ptr(st),
+                                                _stream(self.device)), "tree_trim_flags")
+        return keep, f, st
+
     def graft_check(self, root, radius, terrain, direction, adaptive=False):
         """gbp_tree_graft_check_dev, the graft's stage A, on torch's current
         stream: (attach uint8 [n], actions float64 [n, 10], flags int32 [n])

@@ -495,6 +495,8 @@ class ReplanSession:
         self.T = terrain
         self.adaptive = bool(adaptive)
         self.ws = None
+        self._tree_limit = (0, 0)
+        self.trims_by_search = 0
 
     # -- life cycle ---------------------------------------------------------------
     def begin(self, start, goal, batch=1024, delta=3.0, seed=20251018, init_trees=None,
@@ -588,7 +590,54 @@ class ReplanSession:
                 self.group = min(self.group, (max_halves - (self.half - h0)) & ~1)
             self._run_group()
             self.group = min(self.group * 2, self.g_max)
+            limit, trim_to = self._tree_limit   # the tree limit, once per group
+            if limit > 0 and max(self.known) > limit:
+                self.trim(trim_to)
+                self.trims_by_search += 1
         return self.status["best_a"] >= 0
+
+    # -- the trees bounded --------------------------------------------------------------
+    @property
+    def tree_limit(self):
+        """(max_vertices, trim_to): once per group of halves, when either tree
+        holds more than max_vertices, search calls trim(trim_to).  (0, 0), the
+        default, is off.  Setting it requires 1 <= trim_to <= max_vertices; it
+        is the object's and outlives begin and end."""
+        return self._tree_limit
+
+    @tree_limit.setter
+    def tree_limit(self, value):
+        max_vertices, trim_to = (0, 0) if not value else (int(value[0]), int(value[1]))
+        if max_vertices < 0 or (max_vertices > 0 and not 1 <= trim_to <= max_vertices):
+            raise ValueError("a tree limit needs 1 <= trim_to <= max_vertices")
+        self._tree_limit = (max_vertices, trim_to if max_vertices > 0 else 0)
+
+    def trim(self, max_vertices=0):
+        """Bounds the trees (engine.DeviceTree.trim): both are
+        trimmed in HBM, tree a toward b's root and tree b toward a's, with
+        bound = the held best cost (inf when none is held), at most
+        max_vertices vertices per tree (0: no budget) and the best
+        connection's vertices protected; the list is carried through both
+        device remaps and ranked again.  best_path() and the best cost are
+        bit-identical before and after.  g falls when a later rewire finds a
+        shorter way, so a trimmed vertex might have become useful: the usual
+        anytime-RRT* trade, and opt-in.  Returns (trim stats of tree a and b,
+        shared stats)."""
+        self._need()
+        if max_vertices < 0:
+            raise ValueError("a negative vertex budget")
+        before = list(self.known)
+        st = self.status
+        held = st["best_a"] >= 0 and st["best_b"] >= 0
+        bound = st["best_cost"] if held else float("inf")
+        protect = (st["best_a"], st["best_b"]) if held else (-1, -1)
+        stats = []
+        for k in range(2):
+            buf = self._remap_buf(k, before[k])
+            stats.append(self.trees[k].trim(self.trees[k ^ 1], bound, max_vertices, protect[k],
+                                            remap_dev=buf)[1])
+            self.known[k] = stats[k]["n_kept"]
+        return tuple(stats), self._carry(self._remap[0], self._remap[1], before)
 
     # -- the map changed, the robot moved ----------------------------------------------
     def _remap_buf(self, k, n):

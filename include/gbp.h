@@ -797,6 +797,72 @@ int gbp_tree_graft_keep_host(gbp_terrain *t, gbp_tree *tree, const double *root,
                              int32_t *remap_dev, int64_t remap_cap, gbp_graft_stats *stats,
                              int64_t *n_resolved);
 
+/* ---- a tree trimmed by cost ---------------------------------------
+ * A search kept alive between plans only grows: nothing above removes a vertex
+ * that is still valid.  The trim drops vertices by f[i] = g[i] +
+ * poseDistance(v[i], r), r the other tree's root (its v[0], read on the
+ * device), summed left to right without contraction:
+ *   bound   vertex i >= 1 is over the bound when f[i] > bound.  A NaN f is not;
+ *           a NaN or +inf bound cuts nothing.  With bound = the held best cost
+ *           this is anytime RRT*'s branch-and-bound test: with the current g no
+ *           path through such a vertex beats the held one.
+ *   budget  when max_keep >= 1 and n > max_keep: cut = the element of rank
+ *           max_keep - 1 (0-based, ascending, NaN above +inf) among f[1 .. n),
+ *           and vertex i >= 1 is over the budget when !(f[i] < cut).  A group of
+ *           equal f at the cut goes whole, so at most max_keep - 1 vertices
+ *           besides the root pass; max_keep = 1 leaves the root alone.
+ *           Otherwise cut = +inf and nothing is over the budget.
+ *   protect vertex `protect` and every ancestor of it keep their flag whatever
+ *           their f (-1: none).  The two rows of a connection differ in their
+ *           last bits, so the best connection's own vertex can lie a few ulp
+ *           above the best cost: a session protects best_a / best_b.  With
+ *           protection the tree keeps at most max_keep vertices plus the
+ *           protected chain's length.
+ * g falls when a later rewire finds a shorter way, so a trimmed vertex might
+ * have become useful: the usual anytime-RRT* trade, and opt-in. */
+typedef struct {
+  int64_t n_before;       /* vertices of the tree before the call                        */
+  int64_t n_kept;         /* ... and after stage B (0 from stage A alone)                 */
+  int64_t n_over_bound;   /* vertices with f > bound                                      */
+  int64_t n_over_budget;  /* not over the bound, but over the budget                      */
+  int64_t n_protected;    /* of those two groups: on the protected chain, flag kept       */
+  int64_t n_inherited;    /* dropped by stage B though their own flag is 1 (an ancestor's
+                             is 0; 0 from stage A alone)                                  */
+  int64_t error;          /* stage A: 1 n is not the tree's count, 2 the protected chain
+                             leaves [0, n) or does not reach the root; then keep[] is 0   */
+  double cut;             /* the budget's cut (+inf: no budget applied)                   */
+} gbp_trim_stats;
+/* Stage A: the flags.  Device keep[n] in the form gbp_tree_prune_dev takes as
+ * edge_valid (keep[0] = 1), optionally device f[n] (may be NULL), device
+ * stats[1].  `other` is the other tree's handle (same device); its root does
+ * not come to the host.  The cut is found by a radix select over the 64-bit
+ * order-preserving image of f: integer counts only, so the result does not
+ * depend on scheduling; no host synchronisation between its rounds.
+ * Enqueue-only on `stream`, with the exception gbp_tree_revalidate_dev
+ * documents: f and the select's counts live in the buffer the tree owns for the
+ * prune's rows, grown (which synchronises the device) by a call that finds it
+ * too small, so two stage-A calls on one tree must not be in flight at once.
+ * GBP_E_SHAPE when n exceeds the tree's capacity, GBP_E_INVALID_ARG when
+ * protect is outside [-1, n).  When n is not the device's count nothing of the
+ * tree is read, keep[0] = 0 and stats->error = 1; a protected chain that leaves
+ * the tree gives keep[0] = 0 and stats->error = 2. */
+int gbp_tree_trim_flags_dev(gbp_tree *tree, gbp_tree *other, int64_t n, double bound, int64_t max_keep,
+                            int32_t protect, uint8_t *keep, double *f, gbp_trim_stats *stats,
+                            gbp_stream stream);
+/* Both stages, synchronous, on `stream` (no terrain, no pair check and no
+ * FRAGILE re-decision are involved): stage A, its record read back, then
+ * gbp_tree_prune_dev under the flags.  Host remap[size of the tree before] (may
+ * be NULL) and stats[1], n_kept and n_inherited from the prune's record.  A
+ * failed call leaves the tree as it was: GBP_E_INVALID_ARG for a protect
+ * outside the tree or a protected chain that does not reach the root. */
+int gbp_tree_trim_host(gbp_tree *tree, gbp_tree *other, double bound, int64_t max_keep, int32_t protect,
+                       int32_t *remap, gbp_trim_stats *stats, gbp_stream stream);
+/* The same, with the remap also left in the caller's device array
+ * remap_dev[remap_cap], as gbp_tree_revalidate_keep_host leaves the prune's. */
+int gbp_tree_trim_keep_host(gbp_tree *tree, gbp_tree *other, double bound, int64_t max_keep,
+                            int32_t protect, int32_t *remap, int32_t *remap_dev, int64_t remap_cap,
+                            gbp_trim_stats *stats, gbp_stream stream);
+
 /* ---- the device planner loop (RRTConnectClass::runRRTConnect,
  *      rrt_connect.cpp:230-314, batch-synchronous) ---------------------------
  * One half-iteration, enqueued on `stream` without any host synchronisation:

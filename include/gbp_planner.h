@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <utility>
 #include <vector>
@@ -794,6 +795,17 @@ struct SharedStats {
   int64_t n_dropped_b = 0;  // dropped: only its goal-tree vertex is gone
 };
 
+// What ReplanSession::trim did to one tree (gbp_trim_stats, include/gbp.h).
+struct TrimStats {
+  int64_t n_before = 0;       // vertices before the trim
+  int64_t n_kept = 0;         // ... and after it
+  int64_t n_over_bound = 0;   // vertices with g + h above the held best cost
+  int64_t n_over_budget = 0;  // not over the bound, but outside the vertex budget
+  int64_t n_protected = 0;    // of those two groups: on the best connection's chain, kept
+  int64_t n_inherited = 0;    // dropped only because an ancestor was
+  double cut = std::numeric_limits<double>::infinity();  // the budget's cut in g + h (+inf: none applied)
+};
+
 // The node's loop (terrainMapCallback, then callPlanner on every tick,
 // global_body_planner.cpp:37-131) against one search that stays in HBM: the
 // stream, the plan workspace, both trees and RRT*'s list of kept connections
@@ -838,6 +850,26 @@ struct SharedStats {
 //              list empty: the next search grows it again.
 //   goalAt     the same for a goal that moved, on the goal tree (REVERSE); s
 //              may be valid in STANCE or in FLIGHT, as a goal root may be.
+//   trim       bounds the trees: both are trimmed where they are
+//              (gbp_tree_trim_keep_host), tree a toward b's root and tree b
+//              toward a's, with bound = the held best cost (+inf when none is
+//              held), at most max_vertices vertices per tree (0: no budget)
+//              and the best connection's vertices best_a / best_b protected;
+//              the list is then carried through both device remaps as
+//              mapChanged carries it.  No terrain is involved.  The guarantee:
+//              bestPath and the best cost are bit-identical before and after a
+//              trim (a trim moves rows and changes no g, and the best
+//              connection's two chains are kept whatever their f; with the
+//              budget a tree may therefore keep max_vertices plus its chain's
+//              length).  The heuristic's limit: g falls when a later rewire
+//              finds a shorter way, so a trimmed vertex might have become
+//              useful: the usual anytime-RRT* trade, and opt-in.
+//   setTreeLimit  search then bounds the trees by itself: once per group of
+//              halves, after the group's status read, when either tree holds
+//              more than max_vertices it calls trim(trim_to).  Requires 1 <=
+//              trim_to <= max_vertices; max_vertices = 0 (the default) is off
+//              and changes nothing for a caller that never sets it.  The limit
+//              is the object's: it outlives begin and end.
 //   search's BatchStats: halves and iterations are added per call; rewires,
 //              solutions, targets, extends, attempts_checked, connects,
 //              fragile_resolved, depth_capped, vertices_* and meet_* are set
@@ -870,6 +902,12 @@ class ReplanSession : public RRTStarConnectClass {
                 bool test_edges = false);
   bool goalAt(const State &s, double radius, GraftStats &stats, SharedStats *shared = nullptr,
               bool test_edges = false);
+  // stats (may be null): tree a's record in [0], tree b's in [1]
+  void trim(int64_t max_vertices, TrimStats stats[2], SharedStats *shared = nullptr);
+  void setTreeLimit(int64_t max_vertices, int64_t trim_to);
+  int64_t treeLimit() const { return tree_limit_; }
+  int64_t treeTrimTo() const { return tree_trim_to_; }
+  int64_t trimsBySearch() const { return trims_by_search_; }  // trims the limit has caused
   bool bestPath(std::vector<State> &state_sequence, std::vector<Action> &action_sequence);
   void dump(TreeDump &trees);
   // the kept connections in list order; best (optional): {best_a, best_b} or {-1, -1}
@@ -883,6 +921,7 @@ class ReplanSession : public RRTStarConnectClass {
  private:
   struct Impl;
   Impl *impl_ = nullptr;
+  int64_t tree_limit_ = 0, tree_trim_to_ = 0, trims_by_search_ = 0;
   Impl &impl() const;  // throws EngineError(GBP_E_BAD_HANDLE) before begin
   void carryShared(bool remap_a, bool remap_b, const int64_t n_before[2], SharedStats *shared);
   bool graftTree(int k, const State &s, double radius, GraftStats &stats, SharedStats *shared,

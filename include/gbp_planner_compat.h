@@ -24,6 +24,7 @@ using gbp_amd::PruneStats;
 using gbp_amd::RerootStats;
 using gbp_amd::GraftStats;
 using gbp_amd::SharedStats;
+using gbp_amd::TrimStats;
 namespace planning_utils = gbp_amd::planning_utils;
 using namespace gbp_amd::planning_utils;  // the reference's headers do the same (planning_utils.h)
 
