@@ -193,3 +193,77 @@ def test_post_process_device_equals_host(gpu, algorithm, case, batch, seed, frag
     want = C.oracle_walk(case[0], *C.found_path(case, batch, seed), False)
     assert np.array_equal(bits(dev["states"]), bits(want[0]))
     assert np.array_equal(bits(dev["actions"]), bits(want[1]))
+
+
+# ---- more paths in a call than a launch takes ------------------------------------------------
+def _window_tables(T, paths, adaptive):
+    """The device table of a call of many paths, split per path, its FRAGILE
+    items re-decided as _resolved_table re-decides them."""
+    reached, flags = T.shortcut_table(paths, adaptive=adaptive)
+    reached = reached.cpu().numpy().copy()
+    flags = flags.cpu().numpy().view(np.uint32)
+    assert set(np.unique(reached)) <= {0, 1}
+    assert not np.any(flags & ~np.uint32(L.F_OOD | L.F_NAN | L.F_FRAGILE | L.F_LIMIT))
+    sizes = [len(p) * (len(p) - 1) // 2 for p in paths]
+    assert reached.size == sum(sizes)
+    off = np.r_[0, np.cumsum(sizes)]
+    frag = np.flatnonzero(flags & L.F_FRAGILE)
+    if frag.size:
+        marker = np.zeros((1, 10))
+        marker[0, 6], marker[0, 7] = 0.1, 1.0
+        two = []
+        for it in frag:
+            p = int(np.searchsorted(off, it, side="right")) - 1
+            two.append(paths[p][list(C.pairs(len(paths[p]))[it - off[p]])])
+        out = planner.shortcut_paths(T, two, [marker] * frag.size, adaptive=adaptive)
+        assert out["n_resolved"] == frag.size
+        for it, a in zip(frag, out["actions"]):
+            reached[it] = 1 if a[0, 7] == 0 else 0
+    return [reached[off[p]:off[p + 1]] for p in range(len(paths))], int(frag.size)
+
+
+_singles = {}
+
+
+def _window_reference(dense, adaptive, T):
+    """Per window: (the dense table's sub-block, the oracle's walk, the
+    window's single-path call), once per (path, adaptive)."""
+    key = (dense, adaptive)
+    if key not in _singles:
+        from tests import scale_cases as X
+        case = C.DENSE[dense]
+        n = len(C.dense_path(*case)[0])
+        table = _oracle_table(*case, adaptive)
+        paths, acts = X.window_paths(dense)
+        blocks = [X.window_block(table, n, o, m) for o, m in X.windows(dense)]
+        walks = [C.oracle_walk(case[0][0], S, A, adaptive) for S, A in zip(paths, acts)]
+        ones = [planner.shortcut_paths(T, [S], [A], adaptive=adaptive) for S, A in zip(paths, acts)]
+        _singles[key] = (paths, acts, blocks, walks, ones)
+    return _singles[key]
+
+
+@pytest.mark.parametrize("dense,adaptive,grid", [(0, False, None), (0, True, None), (1, False, None),
+                                                 (1, True, None), (0, False, 2)])
+def test_more_paths_than_a_launch_takes(gpu, monkeypatch, dense, adaptive, grid):
+    """65, 128 and 150 windows of a densified path in one call: two and three
+    launches of up to 64 paths, the later ones carrying the first item and the
+    absolute path and pair offsets of their group.  Every window's table is the
+    dense path's sub-block, its walk the oracle's and its single-path call's."""
+    if grid is not None:     # two workgroups: every wave takes many items of every launch
+        monkeypatch.setenv("GBP_SHORTCUT_GRID", str(grid))
+    from tests import scale_cases as X
+    T = _terrain(C.DENSE[dense][0][0])
+    paths, acts, blocks, walks, ones = _window_reference(dense, adaptive, T)
+    reached_share = np.concatenate(blocks).mean()
+    assert 0.05 <= reached_share <= 0.95
+    for count in X.WINDOW_CALLS:
+        tables, nres = _window_tables(T, paths[:count], adaptive)
+        for p in range(count):
+            assert np.array_equal(tables[p], blocks[p]), (count, p, X.windows(dense)[p], nres)
+        out = planner.shortcut_paths(T, paths[:count], acts[:count], adaptive=adaptive)
+        for p in range(count):
+            _assert_paths_equal(out, p, walks[p], (count, p))
+            for key in ("states", "actions"):
+                assert np.array_equal(bits(ones[p][key][0]), bits(out[key][p])), (count, p, key)
+            for key in ("path_length", "path_yaw", "path_cost"):
+                assert bits(ones[p][key][0]) == bits(out[key][p]), (count, p, key)
