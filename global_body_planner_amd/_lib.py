@@ -51,6 +51,8 @@ EXPORTS = [
     "gbp_sample_actions_host", "gbp_terrain_set_sampling", "gbp_terrain_get_sampling",
     "gbp_sample_states_dir_dev", "gbp_sample_states_dir_host", "gbp_sample_actions_dir_dev",
     "gbp_sample_actions_dir_host",
+    "gbp_informed_ellipse", "gbp_terrain_set_informed", "gbp_terrain_get_informed",
+    "gbp_sample_states_informed_dev", "gbp_sample_states_informed_host",
     "gbp_extend_batch_dev", "gbp_extend_batch_host",
     "gbp_nearest_batch_dev", "gbp_nearest_batch_host",
     "gbp_neighbors_batch_dev", "gbp_neighbors_batch_host", "gbp_knn_batch_dev", "gbp_knn_batch_host",
@@ -82,6 +84,14 @@ class Sampling(ctypes.Structure):
     _fields_ = [("state_flag", ctypes.c_int32), ("state_speed_direction", ctypes.c_int32),
                 ("state_p", ctypes.c_double), ("action_flag", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("action_p", ctypes.c_double)]
+
+
+class Informed(ctypes.Structure):
+    """gbp_informed (include/gbp.h): the ellipse informed sampling draws targets in."""
+    _fields_ = [("active", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("cost", ctypes.c_double), ("cx", ctypes.c_double), ("cy", ctypes.c_double),
+                ("ux", ctypes.c_double), ("uy", ctypes.c_double), ("a", ctypes.c_double),
+                ("b", ctypes.c_double)]
 
 
 class Rect(ctypes.Structure):
@@ -140,6 +150,22 @@ def sampling(state_flag=False, state_p=0.05, speed_direction=False, action_flag=
     """A Sampling record (defaults: the reference's rrt.h:194-200 thresholds, flags off)."""
     return Sampling(int(bool(state_flag)), int(bool(speed_direction)), float(state_p),
                     int(bool(action_flag)), 0, float(action_p))
+
+
+def informed_ellipse(focus_a, focus_b, cost, bounds):
+    """gbp_informed_ellipse (host, no device): the Informed record of two foci
+    (their first two elements: x, y), a cost and the map's bounds
+    {x_0, x_N-1, y_0, y_M-1}; GbpError for what the entry refuses."""
+    import numpy as np
+    fa = np.ascontiguousarray(np.asarray(focus_a, np.float64).ravel()[:2])
+    fb = np.ascontiguousarray(np.asarray(focus_b, np.float64).ravel()[:2])
+    bd = np.ascontiguousarray(bounds, np.float64).reshape(4)
+    out = Informed()
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    rc = load().gbp_informed_ellipse(vp(fa), vp(fb), float(cost), vp(bd), ctypes.byref(out))
+    if rc != OK:
+        raise GbpError(rc, "informed_ellipse")
+    return out
 
 
 class GbpError(RuntimeError):
@@ -206,6 +232,11 @@ def load(path=None):
         "gbp_sample_states_dir_host": (I, [P, I64, U64, U64, I64, P, P, P, P]),
         "gbp_sample_actions_dir_dev": (I, [P, I64, P, P, P, P, I, P, U64, U64, I64, P, P]),
         "gbp_sample_actions_dir_host": (I, [P, I64, P, P, P, P, I, P, U64, U64, I64, P]),
+        "gbp_informed_ellipse": (I, [P, P, ctypes.c_double, P, P]),
+        "gbp_terrain_set_informed": (I, [P, P]),
+        "gbp_terrain_get_informed": (I, [P, P]),
+        "gbp_sample_states_informed_dev": (I, [P, I64, U64, U64, I64, P, P, P, P, P, P]),
+        "gbp_sample_states_informed_host": (I, [P, I64, U64, U64, I64, P, P, P, P, P]),
         "gbp_extend_batch_dev": (I, [P, I64, P, P, P, I, I, U64, I64, P, P, P, P, P, P, P]),
         "gbp_extend_batch_host": (I, [P, I64, P, P, P, I, I, U64, I64, P, P, P, P, P, P]),
         "gbp_resolve_fragile_host": (I, [P, I64, P, P, P, I, I, P, P, P, P, P, P]),

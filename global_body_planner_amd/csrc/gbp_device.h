@@ -897,4 +897,62 @@ __device__ __forceinline__ void sample_state_cfg_try(const TerrainView<ZT> &T, c
     sample_state_try(T, seed, stream_id, index, k, q);
 }
 
+// ---- informed sampling (gbp.h gbp_informed) --------------------------------------
+// Try k of index i: sample_state_try's draws, x and y uniform over the ellipse
+// (sqrt(u) for the radius of the unit disc, scaled by the semi-axes, turned to
+// the foci's axis and moved to the centre) instead of over the map.  sqrt,
+// rm_sincos and + - x only: tests/informed_ref.py reproduces its bits.  A draw
+// outside the map gets a NaN height and is GBP_F_OOD to the state check.
+template <class ZT>
+__device__ __forceinline__ void sample_state_informed_try(const TerrainView<ZT> &T,
+                                                          const gbp_informed &inf, uint64_t seed,
+                                                          uint64_t stream_id, int64_t index, int k,
+                                                          double *q) {
+  const double z_min_rel = H_MIN + ROBOT_H, z_max_rel = H_MAX + ROBOT_H;
+  const double mean = 0.5 * (z_max_rel + z_min_rel);
+  const double sd = (z_max_rel - z_min_rel) * (1.0 / (2 * 3.0));
+  double u00, u01, u10, u11, u20, u21, u30, u31;
+  uniform2(seed, stream_id, PURPOSE_STATE, index, 4u * k + 0, u00, u01);
+  uniform2(seed, stream_id, PURPOSE_STATE, index, 4u * k + 1, u10, u11);
+  uniform2(seed, stream_id, PURPOSE_STATE, index, 4u * k + 2, u20, u21);
+  uniform2(seed, stream_id, PURPOSE_STATE, index, 4u * k + 3, u30, u31);
+  double z0, z1;
+  box_muller(u10, u11, z0, z1);
+  const double hz = z0 * sd + mean;
+  const double r = sqrt(u00);
+  const double th = (2.0 * MY_PI) * u01;
+  double si, co;
+  rm_sincos(th, si, co);
+  const double ex = (inf.a * r) * co, ey = (inf.b * r) * si;
+  q[0] = inf.cx + (inf.ux * ex - inf.uy * ey);
+  q[1] = inf.cy + (inf.uy * ex + inf.ux * ey);
+  double g;
+  bool near = false;
+  if (!height_at(T, q[0], q[1], g, near)) g = __builtin_nan("");
+  q[2] = std_max(std_min(hz, z_max_rel), z_min_rel) + g;
+  const double phi = (2.0 * MY_PI) * u20;
+  const double cos_theta = 2.0 * u21 - 1.0;
+  const double v = u30 * V_MAX;
+  speed_vector(v, cos_theta, phi, q);
+  q[6] = 2 * P_MAX * u31 - P_MAX;
+  q[7] = 0.0;
+}
+
+// sample_state_cfg_try with the handle's ellipse: the coin as there, a coin
+// that lands gives the unchanged direction draw, otherwise the informed draw
+// (active = 0: sample_state_cfg_try, bit for bit)
+template <class ZT>
+__device__ __forceinline__ void sample_state_informed_cfg_try(
+    const TerrainView<ZT> &T, const gbp_sampling &cfg, const gbp_informed &inf,
+    const double *s_from, const double *s_to, uint64_t seed, uint64_t stream_id, int64_t index,
+    int k, double *q) {
+  if (cfg.state_flag && coin(seed, stream_id, index, (uint32_t)k, cfg.state_p))
+    sample_state_direction_try(T, s_from, s_to, cfg.state_speed_direction, seed, stream_id, index,
+                               k, q);
+  else if (inf.active)
+    sample_state_informed_try(T, inf, seed, stream_id, index, k, q);
+  else
+    sample_state_try(T, seed, stream_id, index, k, q);
+}
+
 }  // namespace gbp

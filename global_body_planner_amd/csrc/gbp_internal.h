@@ -11,7 +11,8 @@
 // gbp_terrain.hip: a handle's heights updated in place, its window moved by
 // whole cells and its host mirror;
 // gbp_replan.hip: RRT*'s kept connections carried between searches and the
-// joined path of two device trees): the handles, the block sizes, the device
+// joined path of two device trees;
+// gbp_informed.hip: the handle's informed-sampling ellipse and its sampler): the handles, the block sizes, the device
 // buffers' carve lists, and a tree's allocations and copies.
 // Not part of the C ABI.
 #pragma once
@@ -63,6 +64,7 @@ struct gbp_terrain {
   int64_t opt_xcd_map = 0;          // persistent kernel: slices numbered XCD-major
   int opt_nn_stats = 0;             // 1: the matrix-core NN search counts its fp64 re-checks
   gbp_sampling sampling{};          // direction-biased sampling (gbp_terrain_set_sampling), off
+  gbp_informed informed{};          // informed sampling's ellipse (gbp_terrain_set_informed), off
   int affine = 0;                   // host-verified affine coordinates (both axes)
   int bx = 0, by = 0;
   double ax = 0, hx = 0, ay = 0, hy = 0;

@@ -165,6 +165,53 @@ __global__ __launch_bounds__(TB) void k_targets(TerrainView<ZT> T, gbp_plan_stat
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) commit_targets(st, half, false);
 }
 
+// k_targets with the handle's ellipse active (gbp.h gbp_informed): the same
+// stages, the draws through sample_state_informed_cfg_try.  A kernel of its
+// own, so that k_targets' code stays what it was for every search that does
+// not use the ellipse (one inlined body for both cost k_targets 34 VGPRs and a
+// wave per SIMD): a change to either kernel's stages belongs in both.
+template <class ZT>
+__global__ __launch_bounds__(TB) void k_targets_informed(
+    TerrainView<ZT> T, gbp_plan_status *st, int64_t n, uint64_t seed, uint64_t stream_id,
+    int64_t base, double *__restrict__ cand, uint32_t *__restrict__ cflag,
+    double *__restrict__ targets, _Float16 *__restrict__ tqh, unsigned long long *tiles,
+    uint32_t epoch, int32_t half, uint64_t seq, gbp_sampling cfg, gbp_informed inf,
+    const double *__restrict__ tv, const int32_t *__restrict__ tcount,
+    const double *__restrict__ ov, int direction) {
+  if (gated(st, seq)) return;
+  // direction-biased draws (rrt_connect.cpp:248-252, :283-287): s_from / s_to
+  // are T's last vertex and O's root (FORWARD half, T = Ta), or O's root and
+  // T's last vertex (REVERSE half, T = Tb), as the trees stand when the half
+  // starts (the batch-synchronous snapshot; batch 1 is the reference's loop)
+  const double *t_last = tv + 8 * (int64_t)(*tcount - 1);
+  const double *s_from = direction == GBP_FORWARD ? t_last : ov;
+  const double *s_to = direction == GBP_FORWARD ? ov : t_last;
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  double q[8];
+  uint32_t f = 0;
+  if (i < n) {
+    // randomState with x, y inside the ellipse where the direction coin does not land
+    sample_state_informed_cfg_try(T, cfg, inf, s_from, s_to, seed, stream_id, base + i, 0, q);
+    Acc acc{0, 0, 0};
+    const bool v = is_valid_state(T, q, GBP_STANCE, acc);   // rrt_connect.cpp:254
+    f = acc.flags | (v ? GBP_F_VALID : 0u);
+    copy8(cand + 8 * i, q);
+    cflag[i] = f;
+  }
+  const bool keep = f & GBP_F_VALID;
+  if (__ballot(f & GBP_F_FRAGILE) && (threadIdx.x & (WAVE - 1)) == 0) {  // the targets stage halts
+    atomicOr(&st->halt, (uint32_t)GBP_PLAN_HALT_TARGETS);
+    st->halt_half = half;
+    raise_gate(st, seq);
+  }
+  const uint32_t r = ordered_rank(keep, tiles, epoch, &st->n_targets, st);
+  if (keep) {
+    copy8(targets + 8 * (size_t)r, q);
+    nn_put_hrow(tqh, nullptr, r, q, false);  // the search's query rows
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) commit_targets(st, half, false);
+}
+
 // stage 1 alone (a half resumed after a FRAGILE draw, on the host-patched
 // flags): the compacted targets in draw order and their fp16 query rows
 __global__ __launch_bounds__(CB) void k_compact_targets(gbp_plan_status *st, int64_t n,
@@ -749,7 +796,8 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
     th->half = half;
     HIPCHK(hipEventRecord(th->ev[0], s));
   }
-  if (searched && (!std::is_same_v<ZT, float> || t->sampling.state_flag || t->sampling.action_flag))
+  if (searched && (!std::is_same_v<ZT, float> || t->sampling.state_flag || t->sampling.action_flag ||
+                   t->informed.active))
     return GBP_E_INVALID_ARG;
   if (searched) {
     HIPCHK(hipStreamWaitEvent(s, w->la_done, 0));
@@ -759,7 +807,12 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
       const int rc = la_launch(t, w, O, half + 1, batch, seed, *la, s);
       if (rc) return rc;
     }
-  } else if (run(0) && run(1))  // a fresh half: draws + compaction, one launch
+  } else if (run(0) && run(1) && t->informed.active)  // ... drawn inside the handle's ellipse
+    hipLaunchKernelGGL(k_targets_informed<ZT>, dim3((unsigned)((batch + TB - 1) / TB)), dim3(TB), 0,
+                       s, V, st, batch, seed, target_stream, target_base, w->cand, w->cflag,
+                       w->targets, w->tqh, w->tiles, next_epoch(w), half, ++w->seq, t->sampling,
+                       t->informed, T->v, T->count, O ? O->v : T->v, direction);
+  else if (run(0) && run(1))  // a fresh half: draws + compaction, one launch
     hipLaunchKernelGGL(k_targets<ZT>, dim3((unsigned)((batch + TB - 1) / TB)), dim3(TB), 0, s, V,
                        st, batch, seed, target_stream, target_base, w->cand, w->cflag, w->targets,
                        w->tqh, w->tiles, next_epoch(w), half, ++w->seq, t->sampling, T->v, T->count,
@@ -777,7 +830,8 @@ int enqueue_stages(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *T, gbp_tree *O, int
     if (launch) {
       // the next half's targets drawn beside this search (never direction-biased:
       // s_from / s_to unset) and O's snapshot for its look-ahead search
-      if (!early || t->sampling.state_flag || !O || !std::is_same_v<ZT, float>)
+      if (!early || t->sampling.state_flag || t->informed.active || !O ||
+          !std::is_same_v<ZT, float>)
         return GBP_E_INVALID_ARG;
       prep.dr = la_draw(w, half + 1, batch, *la);
       prep.dr.snap_src = O->count;
@@ -1143,7 +1197,10 @@ int gbp_plan_halves_dev(gbp_terrain *t, gbp_plan_ws *w, gbp_tree *Ta, gbp_tree *
   }();
   // (RRT* too: its insertion rewires the extended tree's parents and g, not
   // its vertices, and the connects still append to O after the snapshot)
+  // (informed targets are drawn by k_targets_informed alone: the search launch's draws
+  // are the plain sampler's, so an active ellipse runs the inline sequence)
   const bool ahead = !la_off && !t->sampling.state_flag && !t->sampling.action_flag &&
+                     !t->informed.active &&
                      t->storage == GBP_STORAGE_F32;  // (k_nn_mfma<float> draws)
   bool searched = false, used = false;
   int rc = GBP_OK;

@@ -574,6 +574,8 @@ void PlannerClass::sync_yaw() {
   }
 }
 
+static bool informedActive(FastTerrainMap &terrain);
+
 State PlannerClass::randomState(FastTerrainMap &terrain) {  // planner_class.cpp:38-76
   State q;
   int32_t tries;
@@ -603,16 +605,37 @@ std::vector<State> PlannerClass::randomStateBatch(FastTerrainMap &terrain, int n
                                                   const State &s_to) {
   std::vector<State> q(n);
   if (n <= 0) return q;
-  chk(gbp_sample_states_dir_host(terrain.handle(), n, seed_, stream_id_, draws_, &cfg,
-                                 s_from.data(), s_to.data(), q[0].data()),
-      "randomState(direction)");
+  if (informedActive(terrain))  // inside the handle's ellipse where the coin does not land
+    chk(gbp_sample_states_informed_host(terrain.handle(), n, seed_, stream_id_, draws_, &cfg,
+                                        nullptr, s_from.data(), s_to.data(), q[0].data()),
+        "randomState(direction, informed)");
+  else
+    chk(gbp_sample_states_dir_host(terrain.handle(), n, seed_, stream_id_, draws_, &cfg,
+                                   s_from.data(), s_to.data(), q[0].data()),
+        "randomState(direction)");
   draws_ += n;
   return q;
+}
+
+// the handle's ellipse (gbp_terrain_set_informed) is active: the batched
+// targets are drawn inside it, as the device loop's k_targets draws them
+static bool informedActive(FastTerrainMap &terrain) {
+  gbp_informed e{};
+  chk(gbp_terrain_get_informed(terrain.handle(), &e), "informed sampling");
+  return e.active != 0;
 }
 
 std::vector<State> PlannerClass::randomStateBatch(FastTerrainMap &terrain, int n) {
   std::vector<State> q(n);
   if (n <= 0) return q;
+  if (informedActive(terrain)) {
+    const gbp_sampling off{};
+    chk(gbp_sample_states_informed_host(terrain.handle(), n, seed_, stream_id_, draws_, &off,
+                                        nullptr, nullptr, nullptr, q[0].data()),
+        "randomStateBatch(informed)");
+    draws_ += n;
+    return q;
+  }
   std::vector<int32_t> tries(n);
   chk(gbp_sample_states_host(terrain.handle(), n, seed_, stream_id_, draws_, -1, 1, q[0].data(),
                              tries.data()),
@@ -754,6 +777,24 @@ gbp_sampling RRTClass::samplingConfig() const {
 void RRTClass::applySampling(FastTerrainMap &terrain) const {
   const gbp_sampling c = samplingConfig();
   chk(gbp_terrain_set_sampling(terrain.handle(), &c), "direction sampling");
+}
+
+RRTClass::InformedScope::InformedScope(const RRTClass &p, FastTerrainMap &terrain,
+                                       const State &s_start, const State &s_goal)
+    : t_(terrain.handle()) {
+  if (!(p.informed_cost_ > 0)) return;  // off: whatever the handle holds applies
+  chk(gbp_terrain_get_informed(t_, &saved_), "informed sampling");
+  double bounds[4];
+  chk(gbp_terrain_info(t_, nullptr, nullptr, nullptr, bounds, nullptr), "informed sampling");
+  gbp_informed e{};
+  chk(gbp_informed_ellipse(s_start.data(), s_goal.data(), p.informed_cost_, bounds, &e),
+      "informed sampling");
+  chk(gbp_terrain_set_informed(t_, &e), "informed sampling");
+  set_ = true;
+}
+
+RRTClass::InformedScope::~InformedScope() {
+  if (set_) (void)gbp_terrain_set_informed(t_, &saved_);
 }
 
 void RRTClass::initTreePair(PlannerClass &Ta, PlannerClass &Tb, const State &s_start,
@@ -1501,6 +1542,7 @@ bool RRTConnectClass::buildRRTConnectBatched(FastTerrainMap &terrain, State s_st
                                              std::vector<State> &state_sequence,
                                              std::vector<Action> &action_sequence,
                                              BatchStats *stats) {
+  const InformedScope informed(*this, terrain, s_start, s_goal);  // set_informed_cost, for this run
   const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
@@ -1760,6 +1802,7 @@ bool RRTConnectClass::buildRRTConnectDevice(FastTerrainMap &terrain, State s_sta
                                             std::vector<Action> &action_sequence,
                                             BatchStats *stats, uint64_t stream_a,
                                             uint64_t stream_b) {
+  const InformedScope informed(*this, terrain, s_start, s_goal);  // set_informed_cost, for this run
   const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
@@ -2125,6 +2168,7 @@ bool RRTStarConnectClass::buildRRTStarConnectBatched(FastTerrainMap &terrain, St
                                                      std::vector<State> &state_sequence,
                                                      std::vector<Action> &action_sequence,
                                                      BatchStats *stats) {
+  const InformedScope informed(*this, terrain, s_start, s_goal);  // set_informed_cost, for this run
   const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
@@ -2186,6 +2230,7 @@ bool RRTStarConnectClass::buildRRTStarConnectDevice(FastTerrainMap &terrain, Sta
                                                     std::vector<State> &state_sequence,
                                                     std::vector<Action> &action_sequence,
                                                     BatchStats *stats) {
+  const InformedScope informed(*this, terrain, s_start, s_goal);  // set_informed_cost, for this run
   const Stopwatch clk;
   goal_found = false;
   wall_to_first_ = -1;
@@ -2254,17 +2299,64 @@ struct ReplanSession::Impl {
   DeviceBuffer remap[2];   // the last prune's / re-root's device remaps (int32)
   DeviceBuffer stats;      // gbp_shared_stats[1]
   int64_t path_cap = 256;  // rows bestPath asks for first (grown to the length needed)
+  gbp_informed saved_informed{};  // what the handle held at begin (setInformed)
+  bool informed_set = false;      // the session has written the handle's ellipse
+  State root[2];                  // the trees' roots as updateInformed last read them
+  bool roots_known = false;       // (cleared by every carry: the upkeep calls move a root)
   ~Impl() {
     if (S.stream) gbp_stream_synchronize(S.stream);  // before the buffers go
   }
 };
 
 ReplanSession::ReplanSession() = default;
-ReplanSession::~ReplanSession() { end(); }
-
-void ReplanSession::end() {
+// (the destructor does not touch the terrain handle, which may be gone by
+// then: only an explicit end() puts the handle's ellipse back)
+ReplanSession::~ReplanSession() {
   delete impl_;
   impl_ = nullptr;
+}
+
+void ReplanSession::end() {
+  if (impl_ && impl_->informed_set) (void)gbp_terrain_set_informed(impl_->S.h, &impl_->saved_informed);
+  delete impl_;
+  impl_ = nullptr;
+}
+
+void ReplanSession::setInformed(bool on) {
+  informed_ = on;
+  if (!impl_) return;
+  if (on) {
+    updateInformed();
+  } else if (impl_->informed_set) {
+    chk(gbp_terrain_set_informed(impl_->S.h, &impl_->saved_informed), "ReplanSession: informed");
+    impl_->informed_set = false;
+  }
+}
+
+gbp_informed ReplanSession::informedState() const {
+  gbp_informed e{};
+  chk(gbp_terrain_get_informed(impl().S.h, &e), "ReplanSession: informed");
+  return e;
+}
+
+// the ellipse of the two roots and the best cost held, or off while none is
+void ReplanSession::updateInformed() {
+  if (!informed_ || !impl_) return;
+  DeviceSearch &S = impl_->S;
+  gbp_informed e{};
+  if (S.ps.best_a >= 0 && S.ps.best_b >= 0 && S.ps.best_cost < std::numeric_limits<double>::infinity()) {
+    // the search never moves a root: read once, and again after an upkeep call
+    for (int k = 0; k < 2 && !impl_->roots_known; k++)
+      chk(gbp_tree_read(S.tree[k], 0, 1, impl_->root[k].data(), nullptr, nullptr, nullptr, S.stream),
+          "ReplanSession: root");
+    impl_->roots_known = true;
+    double bounds[4];
+    chk(gbp_terrain_info(S.h, nullptr, nullptr, nullptr, bounds, nullptr), "ReplanSession: informed");
+    chk(gbp_informed_ellipse(impl_->root[0].data(), impl_->root[1].data(), S.ps.best_cost, bounds, &e),
+        "ReplanSession: informed");
+  }
+  chk(gbp_terrain_set_informed(S.h, &e), "ReplanSession: informed");
+  impl_->informed_set = true;
 }
 
 ReplanSession::Impl &ReplanSession::impl() const {
@@ -2304,7 +2396,9 @@ void ReplanSession::begin(FastTerrainMap &terrain, State s_start, State s_goal, 
   open_search(S, terrain.device(), none, s_start, s_goal, extend_counter_);
   I->stats.reserve(terrain.device(), 1, sizeof(gbp_shared_stats), 1, "ReplanSession: stats");
   chk(gbp_plan_status_read(S.ws, &S.ps, S.stream), "plan status");
+  chk(gbp_terrain_get_informed(S.h, &I->saved_informed), "ReplanSession: informed");
   impl_ = I.release();
+  updateInformed();
 }
 
 bool ReplanSession::search(double max_time, int64_t max_halves, BatchStats *stats) {
@@ -2333,6 +2427,7 @@ bool ReplanSession::search(double max_time, int64_t max_halves, BatchStats *stat
       trim(tree_trim_to_, nullptr);
       trims_by_search_++;
     }
+    updateInformed();  // the next group's targets: inside the best cost's ellipse
   }
   extend_counter_ = ps.ext_counter;
   rewires_ = ps.stat_rewires;
@@ -2386,6 +2481,8 @@ void ReplanSession::carryShared(bool remap_a, bool remap_b, const int64_t n_befo
     shared->n_dropped_a = hs.n_dropped_a;
     shared->n_dropped_b = hs.n_dropped_b;
   }
+  impl_->roots_known = false;  // a re-root or a graft moves a root
+  updateInformed();            // ... and the best cost may have changed
 }
 
 void ReplanSession::mapChanged(FastTerrainMap &terrain, PruneStats stats[2], SharedStats *shared) {

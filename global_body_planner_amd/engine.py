@@ -342,6 +342,33 @@ class Terrain:
             _np_ptr(f), _np_ptr(t), _ptr(st), _stream(self.device)), "sample_states_dir")
         return st
 
+    # ---- informed sampling (gbp_informed): targets inside the best cost's ellipse ----
+    def set_informed(self, inf=None):
+        """Install a _lib.Informed (L.informed_ellipse) on the handle (None: off);
+        the device planner loop's targets and the host planner's are drawn in it."""
+        check(self._lib.gbp_terrain_set_informed(self._h, None if inf is None else ctypes.byref(inf)),
+              "set_informed")
+
+    def get_informed(self):
+        inf = L.Informed()
+        check(self._lib.gbp_terrain_get_informed(self._h, ctypes.byref(inf)), "get_informed")
+        return inf
+
+    def sample_states_informed(self, n, seed, stream_id, s_from=None, s_to=None, index_base=0,
+                               cfg=None, inf=None):
+        """sample_states_dir's draws with x, y uniform over the ellipse where the
+        coin does not pick the direction draw; cfg, inf None: the handle's.
+        s_from / s_to are needed only when cfg's state_flag is on."""
+        st = self._empty((n, 8), torch.float64)
+        f = None if s_from is None else np.ascontiguousarray(s_from, np.float64).reshape(8)
+        t = None if s_to is None else np.ascontiguousarray(s_to, np.float64).reshape(8)
+        check(self._lib.gbp_sample_states_informed_dev(
+            self._h, n, seed, stream_id, index_base, None if cfg is None else ctypes.byref(cfg),
+            None if inf is None else ctypes.byref(inf), None if f is None else _np_ptr(f),
+            None if t is None else _np_ptr(t), _ptr(st), _stream(self.device)),
+            "sample_states_informed")
+        return st
+
     def sample_actions_dir(self, normals, s, s_near, direction, seed, stream_id, index_base=0,
                            cfg=None):
         """getRandomAction(surf_norm, direction, flag, p, s, s_near)

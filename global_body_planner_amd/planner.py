@@ -497,6 +497,9 @@ class ReplanSession:
         self.ws = None
         self._tree_limit = (0, 0)
         self.trims_by_search = 0
+        self._informed = False
+        self._informed_set = False   # the session has written the handle's ellipse
+        self._roots = None           # the trees' roots as _update_informed last read them
 
     # -- life cycle ---------------------------------------------------------------
     def begin(self, start, goal, batch=1024, delta=3.0, seed=20251018, init_trees=None,
@@ -534,11 +537,59 @@ class ReplanSession:
         self.g_max = max(2, min(64, (1 << 21) // self.batch)) & ~1
         self.status = self.ws.status(self.T.device)
         self._remap = [None, None]
+        self._saved_informed = self.T.get_informed()
+        self._roots = None
+        self._update_informed()
         return self
 
     def end(self):
+        if self.ws is not None and self._informed_set:
+            self.T.set_informed(self._saved_informed)
+        self._informed_set = False
         self.ws = None
         self.trees = None
+
+    # -- informed sampling ------------------------------------------------------------
+    @property
+    def informed(self):
+        """Informed sampling, off by default; the object's, like
+        the tree limit.  When on, the session keeps the ellipse of (tree a's
+        root, tree b's root, the status's best cost, the map's bounds) on the
+        terrain handle: computed once per group of halves after the group's
+        status read and after map_changed, robot_at, robot_off, goal_at and
+        trim; off while no connection is held.  end() puts back what the handle
+        held at begin; turning the property off restores it at once."""
+        return self._informed
+
+    @informed.setter
+    def informed(self, on):
+        self._informed = bool(on)
+        if self.ws is None:
+            return
+        if self._informed:
+            self._update_informed()
+        elif self._informed_set:
+            self.T.set_informed(self._saved_informed)
+            self._informed_set = False
+
+    @property
+    def informed_state(self):
+        """The _lib.Informed in force on the terrain handle."""
+        self._need()
+        return self.T.get_informed()
+
+    def _update_informed(self):
+        if not self._informed or self.ws is None:
+            return
+        st = self.status
+        e = _lib.Informed()
+        if st["best_a"] >= 0 and st["best_b"] >= 0 and st["best_cost"] < float("inf"):
+            if self._roots is None:   # the search never moves a root: read again after upkeep only
+                self._roots = [t.read_state(0) for t in self.trees]
+            e = _lib.informed_ellipse(self._roots[0], self._roots[1], st["best_cost"],
+                                      self.T.info()["bounds"])
+        self.T.set_informed(e)
+        self._informed_set = True
 
     @property
     def active(self):
@@ -594,6 +645,7 @@ class ReplanSession:
             if limit > 0 and max(self.known) > limit:
                 self.trim(trim_to)
                 self.trims_by_search += 1
+            self._update_informed()   # the next group's targets: inside the best cost's ellipse
         return self.status["best_a"] >= 0
 
     # -- the trees bounded --------------------------------------------------------------
@@ -653,6 +705,8 @@ class ReplanSession:
         self.status = self.ws.status(self.T.device)
         if st["error"]:
             raise _lib.GbpError(_lib.E_INVALID_ARG, "kept connections: an index outside its tree")
+        self._roots = None        # a re-root or a graft moves a root
+        self._update_informed()   # ... and the best cost may have changed
         return st
 
     def map_changed(self):

@@ -417,6 +417,62 @@ int gbp_sample_actions_dir_host(gbp_terrain *t, int64_t n, const double *normals
                                 const gbp_sampling *cfg, uint64_t seed, uint64_t stream_id,
                                 int64_t index_base, double *actions);
 
+/* ---- informed sampling: targets inside the best cost's ellipse -------------
+ * Path cost is a sum of poseDistance (3-D) and a 2-D distance never exceeds
+ * the 3-D one, so a state on a path shorter than c between the two trees'
+ * roots A and B satisfies |p.xy - A.xy| + |p.xy - B.xy| < c: an ellipse in xy
+ * with foci A.xy, B.xy and major axis c, a superset of the 3-D informed set.
+ * Off by default: the reference draws over the whole map. */
+typedef struct {
+  int32_t active;    /* 0: draws are the plain sampler's */
+  int32_t reserved;
+  double cost;       /* c */
+  double cx, cy;     /* centre */
+  double ux, uy;     /* unit vector focus a -> focus b in xy; (1, 0) when they coincide */
+  double a, b;       /* semi-axes */
+} gbp_informed;
+/* The ellipse of two foci and a cost (host, no device call); focus_a, focus_b:
+ * at least [2] (x, y); bounds = gbp_terrain_info's {x_0, x_N-1, y_0, y_M-1}.
+ * binary64, each step its own rounding:
+ *   dx = bx - ax; dy = by - ay; d = sqrt(dx*dx + dy*dy);
+ *   ux = d > 0 ? dx / d : 1; uy = d > 0 ? dy / d : 0;
+ *   cx = (ax + bx) * 0.5; cy = (ay + by) * 0.5;
+ *   a = cost * 0.5; w = cost*cost - d*d; b = w > 0 ? sqrt(w) * 0.5 : 0;
+ *   active = cost < INFINITY && (MY_PI * a) * b < (bounds[1]-bounds[0]) * (bounds[3]-bounds[2])
+ * (uniform draws in the ellipse beat uniform draws in the map exactly when the
+ * ellipse is the smaller; MY_PI is the planner's 3.14159).  cost = +inf:
+ * active 0 with the other fields filled; cost below d: b = 0, the segment
+ * between the foci.  GBP_E_INVALID_ARG for a null pointer, a NaN among the four
+ * focus coordinates, a NaN cost or cost <= 0 (*out untouched). */
+int gbp_informed_ellipse(const double *focus_a, const double *focus_b, double cost,
+                         const double bounds[4], gbp_informed *out);
+/* The handle's ellipse (NULL = off), per handle like gbp_sampling: applied to
+ * the device planner loop's targets (gbp_plan_half_dev, gbp_plan_halves_dev;
+ * a half with `active` set runs the inline sequence, without the look-ahead
+ * search) and to the host planner's.  GBP_E_INVALID_ARG for an active ellipse
+ * with a NaN field or a negative semi-axis. */
+int gbp_terrain_set_informed(gbp_terrain *t, const gbp_informed *inf);
+int gbp_terrain_get_informed(const gbp_terrain *t, gbp_informed *inf);
+/* Index i of stream with gbp_sample_states_dir_dev's draws (one try, the same
+ * eight uniforms of PURPOSE_STATE) and arguments; where the coin does not pick
+ * the direction draw and inf->active is set, x and y are uniform over the
+ * ellipse instead of the map:
+ *   r = sqrt(u00); th = (2.0 * MY_PI) * u01; (si, co) = sincos(th);
+ *   ex = (a * r) * co; ey = (b * r) * si;
+ *   x = cx + (ux * ex - uy * ey); y = cy + (uy * ex + ux * ey);
+ * height (NaN outside the map: such a state is GBP_F_OOD to the state check),
+ * velocity, pitch and q[7] as gbp_sample_states_dev forms them.  active = 0:
+ * gbp_sample_states_dir_dev's draws bit for bit.  cfg, inf NULL = the
+ * handle's; s_from, s_to may be NULL when cfg's state_flag is off. */
+int gbp_sample_states_informed_dev(gbp_terrain *t, int64_t n, uint64_t seed, uint64_t stream_id,
+                                   int64_t index_base, const gbp_sampling *cfg,
+                                   const gbp_informed *inf, const double *s_from,
+                                   const double *s_to, double *states, gbp_stream stream);
+int gbp_sample_states_informed_host(gbp_terrain *t, int64_t n, uint64_t seed, uint64_t stream_id,
+                                    int64_t index_base, const gbp_sampling *cfg,
+                                    const gbp_informed *inf, const double *s_from,
+                                    const double *s_to, double *states);
+
 /* ---- batched extend (RRTClass::newConfig + the acceptance half of
  *      RRTClass::extend, rrt.cpp:20-102) --------------------------------------
  * For extend i: s_near[i] (the nearest vertex, found by gbp_nearest_batch),

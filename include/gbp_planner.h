@@ -409,6 +409,12 @@ class RRTClass {
     state_direction_sampling_probability_threshold_ = threshold;
     state_direction_sampling_speed_direction_flag_ = speed_direction_flag;
   }
+  // informed sampling (gbp.h gbp_informed; 0 = off, the reference's behaviour):
+  // the batched and the device-resident searches draw their targets inside the
+  // ellipse of (s_start, s_goal, cost), fixed for the whole run, so both draw
+  // the same targets; any cost at or above a known path's is admissible
+  void set_informed_cost(double cost) { informed_cost_ = cost; }
+  double informedCost() const { return informed_cost_; }
   void print_setting_parameters();
   void set_state_action_pair_check_adaptive_step_size_flag_(bool f) {
     state_action_pair_check_adaptive_step_size_flag_ = f;
@@ -440,6 +446,23 @@ class RRTClass {
   // installs samplingConfig() on the terrain handle (the candidate sampler and
   // the device loop's targets read it there)
   void applySampling(FastTerrainMap &terrain) const;
+  // set_informed_cost's ellipse on the terrain handle for the lifetime of the
+  // object (a build call); the handle's own setting comes back afterwards.
+  // With the cost off nothing is touched.
+  class InformedScope {
+   public:
+    InformedScope(const RRTClass &p, FastTerrainMap &terrain, const State &s_start,
+                  const State &s_goal);
+    ~InformedScope();
+    InformedScope(const InformedScope &) = delete;
+    InformedScope &operator=(const InformedScope &) = delete;
+
+   private:
+    gbp_terrain *t_;
+    gbp_informed saved_{};
+    bool set_ = false;
+  };
+  double informed_cost_ = 0;
   // a search's two trees from their roots: Ta at s_start drawing from Philox
   // stream stream_a of this planner's seed, Tb at s_goal from stream_b
   void initTreePair(PlannerClass &Ta, PlannerClass &Tb, const State &s_start, const State &s_goal,
@@ -908,6 +931,23 @@ class ReplanSession : public RRTStarConnectClass {
   int64_t treeLimit() const { return tree_limit_; }
   int64_t treeTrimTo() const { return tree_trim_to_; }
   int64_t trimsBySearch() const { return trims_by_search_; }  // trims the limit has caused
+  // Informed sampling (gbp.h gbp_informed), off by default; the
+  // object's, like the tree limit: it outlives begin and end.  When on, the
+  // session keeps the ellipse of (tree a's root, tree b's root, the status's
+  // best cost, the map's bounds) on the terrain handle: computed once per
+  // group of halves after the group's status read (where the tree limit is
+  // tested) and after mapChanged, both robotAt, robotOff, goalAt and trim;
+  // while no connection is held the handle's ellipse is off and the search is
+  // the plain one, bit for bit.  The value is up to one group stale; the best
+  // cost only falls and any cost at or above it is admissible.  It changes
+  // only between groups, so a search of a given number of halves is
+  // reproducible.  end() puts back what the handle held at begin (the terrain
+  // must be alive then); the destructor does not touch the handle, so a session
+  // destroyed without end() leaves its last ellipse there.  Turning it off
+  // restores the handle's setting at once.
+  void setInformed(bool on);
+  bool informed() const { return informed_; }
+  gbp_informed informedState() const;  // the handle's ellipse in force
   bool bestPath(std::vector<State> &state_sequence, std::vector<Action> &action_sequence);
   void dump(TreeDump &trees);
   // the kept connections in list order; best (optional): {best_a, best_b} or {-1, -1}
@@ -922,6 +962,8 @@ class ReplanSession : public RRTStarConnectClass {
   struct Impl;
   Impl *impl_ = nullptr;
   int64_t tree_limit_ = 0, tree_trim_to_ = 0, trims_by_search_ = 0;
+  bool informed_ = false;
+  void updateInformed();  // the ellipse from the status as it stands (informed_ on)
   Impl &impl() const;  // throws EngineError(GBP_E_BAD_HANDLE) before begin
   void carryShared(bool remap_a, bool remap_b, const int64_t n_before[2], SharedStats *shared);
   bool graftTree(int k, const State &s, double radius, GraftStats &stats, SharedStats *shared,
