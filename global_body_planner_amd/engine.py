@@ -941,7 +941,8 @@ def nearest(queries, vertices):
 
 def neighbors(queries, vertices, radius, max_out=256):
     """Batched PlannerClass::neighborhoodDist (planner_class.cpp:173-182):
-    (idx [n, max_out] int32, -1 padded, ascending vertex index; count [n])."""
+    (idx [n, max_out] int32, -1 padded, in the order the reference's vertex map
+    iterates keys 0..n_vert-1, gbp_vertex_map_order; count [n])."""
     lib = L.load()
     q = queries.contiguous()
     v = vertices.contiguous()

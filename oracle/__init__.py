@@ -4,11 +4,11 @@ TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg, never by the product package
 (global_body_planner_amd/), which must fail loudly without its HIP library.
 
-Parity status: the reference's tests pin nothing and the reference cannot be
-compiled in this image (its headers include ROS / grid_map / Eigen), so
-bit-level parity against reference OUTPUTS is unpinned; see DESIGN.md and
-tests/test_oracle_pins.py for the survey-recorded reference outputs this
-restatement is pinned to.
+Parity status: tests/test_reference_parity.py compares this restatement, bit
+for bit, with what the reference's own sources compute (recorded in
+tests/golden/reference_vectors.npz by tools/make_ref_golden.py through
+oracle/ref/ and oracle/reflib.py); DESIGN.md section 3 lists what that pins and
+what it does not.  tests/test_oracle_pins.py keeps the survey-recorded outputs.
 """
 import ctypes
 import os
@@ -69,6 +69,8 @@ def lib():
             "orc_state_distance": (D, [P, P]),
             "orc_state_yaw_distance": (D, [P, P]),
             "orc_attempt_connect": (I, [P, P, P, D, P, P, I, I]),
+            "orc_attempt_connect_info": (I, [P, P, P, D, P, P, I, I, P]),
+            "orc_rotate_grf": (None, [P, P, P]),
             "orc_validate_pairs": (None, [P, I64, P, P, P, I, I, P, P, P, P, P, I]),
             "orc_valid_states": (None, [P, I64, P, P, I, P, P, P, I]),
             "orc_height_batch": (None, [P, I64, P, P, P, P, I]),
@@ -371,6 +373,29 @@ class OracleTerrain:
         r = lib().orc_attempt_connect(self.ref, _p(s_existing), _p(s), float(t_s), _p(s_new),
                                       _p(a_new), int(direction), int(bool(adaptive)))
         return r, s_new, a_new
+
+
+    def attempt_connect_info(self, s_existing, s, direction, t_s=0.0, adaptive=False,
+                             s_new_init=None, a_new_init=None):
+        """attempt_connect plus where the reference's result is undefined:
+        (result, s_new, a_new, flags, undefined, checks): flags the union of
+        every level's pair-check flags, undefined bit 0 the depth cap / bit 1 an
+        unassigned s_new or t_new that the recursion would consume."""
+        s_existing = _c(s_existing, np.float64)
+        s = _c(s, np.float64)
+        s_new = np.full(8, np.nan) if s_new_init is None else _c(s_new_init, np.float64).copy()
+        a_new = np.full(10, np.nan) if a_new_init is None else _c(a_new_init, np.float64).copy()
+        info = np.zeros(3, np.uint32)
+        r = lib().orc_attempt_connect_info(self.ref, _p(s_existing), _p(s), float(t_s), _p(s_new),
+                                           _p(a_new), int(direction), int(bool(adaptive)), _p(info))
+        return r, s_new, a_new, int(info[0]), int(info[1]), int(info[2])
+
+
+def rotate_grf(normal, f):
+    """planning_utils.cpp:198-231 (orc_rotate_grf)."""
+    o = np.empty(3)
+    lib().orc_rotate_grf(_p(_c(normal, np.float64)), _p(_c(f, np.float64)), _p(o))
+    return o
 
 
 def _path_from_start(tree, idx):  # rrt.cpp:107-118

@@ -595,6 +595,8 @@ static void connect_action(const double *s_start, const double *s_goal, double t
 typedef struct {
   int capped;     /* the recursion reached GBP_CONNECT_MAX_DEPTH */
   int64_t checks; /* pair checks run (the engine's attempts_checked) */
+  uint32_t flags; /* union of the levels' pair-check flags */
+  int unset;      /* a failed check left s_new / t_new unassigned (reference: UB) */
 } ac_stats;
 
 static int attempt_connect_ts(const orc_terrain *T, const double *s_existing, const double *s,
@@ -620,11 +622,15 @@ static int attempt_connect_ts(const orc_terrain *T, const double *s_existing, co
     int ok = (direction == GBP_FORWARD)
                  ? orc_is_valid_pair(T, s_start, a_new, GBP_FORWARD, adaptive, s_new, &t_new, &f, 0)
                  : orc_is_valid_pair(T, s_goal, a_new, GBP_REVERSE, adaptive, s_new, &t_new, &f, 0);
+    if (acs) acs->flags |= f;
     if (ok) return GBP_REACHED;
     /* The reference recurses with t_new / s_new even when the failed check
      * never assigned them (uninitialised locals: UB).
      * Convention shared with the engine: that case is TRAPPED. */
-    if (!(f & GBP_F_TNEW_SET) || !(f & GBP_F_SNEW_SET)) return GBP_TRAPPED;
+    if (!(f & GBP_F_TNEW_SET) || !(f & GBP_F_SNEW_SET)) {
+      if (acs) acs->unset = 1;
+      return GBP_TRAPPED;
+    }
     double s_mid[8];
     memcpy(s_mid, s_new, sizeof s_mid);
     if (attempt_connect_ts(T, s_existing, s_mid, t_new, s_new, a_new, direction, adaptive,
@@ -639,6 +645,22 @@ int orc_attempt_connect(const orc_terrain *T, const double *s_existing, const do
                         double t_s, double *s_new, double *a_new, int direction, int adaptive) {
   if (!(t_s > 0)) t_s = orc_pose_distance(s, s_existing) / V_NOM; /* rrt_connect.cpp:89 */
   return attempt_connect_ts(T, s_existing, s, t_s, s_new, a_new, direction, adaptive, 0, 0);
+}
+
+/* the same walk, reporting where the reference's result is undefined:
+ * info[0] the union of every level's pair-check flags (GBP_F_OOD, ...),
+ * info[1] bit 0 the depth cap was reached, bit 1 an unassigned s_new / t_new
+ * would have been consumed, info[2] the pair checks run */
+int orc_attempt_connect_info(const orc_terrain *T, const double *s_existing, const double *s,
+                             double t_s, double *s_new, double *a_new, int direction,
+                             int adaptive, uint32_t *info) {
+  ac_stats acs = {0, 0, 0, 0};
+  if (!(t_s > 0)) t_s = orc_pose_distance(s, s_existing) / V_NOM;
+  int r = attempt_connect_ts(T, s_existing, s, t_s, s_new, a_new, direction, adaptive, 0, &acs);
+  info[0] = acs.flags;
+  info[1] = (uint32_t)(acs.capped ? 1 : 0) | (uint32_t)(acs.unset ? 2 : 0);
+  info[2] = (uint32_t)acs.checks;
+  return r;
 }
 
 /* ---- batch helpers ------------------------------------------------------ */
@@ -1708,7 +1730,7 @@ int orc_plan(const orc_terrain *T, const double *start, const double *goal,
       double *sn = it_sn + 8 * (int64_t)i, *an = it_an + 10 * (int64_t)i;
       memset(sn, 0, 8 * sizeof(double));
       memset(an, 0, 10 * sizeof(double));
-      ac_stats acs = {0, 0};
+      ac_stats acs = {0, 0, 0, 0};
       it_r[i] = attempt_connect_ts(T, s_ex, q, orc_pose_distance(q, s_ex) / V_NOM, sn, an, cdir,
                                    cfg->adaptive, 0, &acs);
       it_nn[i] = nn;

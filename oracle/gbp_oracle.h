@@ -14,12 +14,12 @@
  * bisection that returns the identical bracket (used only to make big parity
  * runs finish quickly).
  *
- * Parity status: the reference's own tests pin nothing (test/
- * test_global_body_planner.cpp asserts 1+1==2) and the reference cannot be
- * compiled here (its headers need ROS / grid_map / Eigen, absent from the
- * image), so bit-level parity against reference *outputs* is UNPINNED; the
- * restatement is pinned against the survey-recorded outputs of the compiled
- * reference in tests/test_oracle_pins.py.  See DESIGN.md.
+ * Parity status: the reference's ROS-free sources are compiled with stand-in
+ * headers (oracle/ref/, `make ref`) and their outputs recorded in
+ * tests/golden/reference_vectors.npz; tests/test_reference_parity.py holds this
+ * restatement to them bit for bit on the deterministic surface (DESIGN.md
+ * section 3 says what is pinned and what is not).  The survey-recorded outputs
+ * of SURVEY.md stay pinned in tests/test_oracle_pins.py.
  */
 #ifndef GBP_ORACLE_H
 #define GBP_ORACLE_H
@@ -94,6 +94,11 @@ int orc_extend(const orc_terrain *T, const double *s_near, const double *target,
 int orc_attempt_connect(const orc_terrain *T, const double *s_existing, const double *s,
                         double t_s, double *s_new, double *a_new, int direction,
                         int adaptive);
+/* the same walk with info[3]: the union of the levels' pair-check flags, bit 0
+ * depth cap reached / bit 1 unassigned s_new or t_new consumed, checks run */
+int orc_attempt_connect_info(const orc_terrain *T, const double *s_existing, const double *s,
+                             double t_s, double *s_new, double *a_new, int direction,
+                             int adaptive, uint32_t *info);
 
 /* ---- batch helpers (OpenMP over independent items, nthreads <= 0 => 1) --- */
 void orc_validate_pairs(const orc_terrain *T, int64_t n, const double *s, const double *a,

@@ -1,7 +1,8 @@
 """Pin the CPU restatement to outputs of the compiled reference recorded in
-SURVEY.md (§6, §8(a), §8(d), H8, H12) — the only reference outputs that exist:
-the reference's own tests pin nothing and the reference cannot be compiled in
-this image.  Each test cites where the survey recorded the value."""
+SURVEY.md (§6, §8(a), §8(d), H8, H12), recorded from the full ROS build during
+the survey; the reference's own tests pin nothing.  (Bit-level parity with the
+reference's ROS-free sources is tests/test_reference_parity.py.)  Each test
+cites where the survey recorded the value."""
 import numpy as np
 import pytest
 

@@ -1,8 +1,9 @@
 """Generate tests/golden/oracle_vectors.npz from the CPU restatement.
 
-The reference's own tests pin nothing (test/test_global_body_planner.cpp
-asserts 1+1==2) and the reference cannot be built here, so these vectors
-freeze the oracle's outputs (glibc 2.35 libm, -ffp-contract=off) so that any
+These vectors freeze the oracle's own outputs on tens of thousands of cases;
+parity with the compiled reference is the business of
+tools/make_ref_golden.py and tests/test_reference_parity.py, which reuse the
+inputs recorded here.  They freeze the outputs (glibc 2.35 libm, -ffp-contract=off) so that any
 later change to the restatement or the engine that moves a decision, a flag,
 a lookup count or a bit of s_new / t_new is caught.  Inputs are small
 (tens of thousands of cases); every array is plain data (np.savez, no pickle).
