@@ -29,6 +29,8 @@ OPT_NN_STATS = 18
 OPT_REFILL_WINDOW = 19
 OPT_LAUNCH_BLOCK = 20
 OPT_NAN_FREE, OPT_NAN_TESTS = 21, 22
+OPT_DERIVE_SLOPES = 23
+SLOPES_F32 = 2  # derive_slopes flag; OPT_DERIVE_SLOPES takes 1 | flags
 PLAN_HALT_TARGETS, PLAN_HALT_EXTEND, PLAN_HALT_CONNECT = 1, 2, 4
 PLAN_HALT_STAR, PLAN_HALT_STAR_PAIRS = 8, 16
 KERNEL_DIRECT, KERNEL_PERSISTENT = 0, 1
@@ -42,6 +44,8 @@ EXPORTS = [
     "gbp_terrain_create", "gbp_terrain_destroy", "gbp_terrain_info",
     "gbp_terrain_update_dev", "gbp_terrain_update_host", "gbp_terrain_read_host",
     "gbp_terrain_move_host", "gbp_terrain_move_shift_ms", "gbp_coord_shift",
+    "gbp_terrain_derive_slopes_dev", "gbp_terrain_derive_slopes_host",
+    "gbp_terrain_read_slopes_host",
     "gbp_terrain_set_option", "gbp_terrain_get_option", "gbp_validate_lds_plan",
     "gbp_height_batch_dev", "gbp_height_batch_host",
     "gbp_normal_batch_dev", "gbp_normal_batch_host",
@@ -211,6 +215,9 @@ def load(path=None):
         "gbp_terrain_move_host": (I, [P, I64, I64, P, P, I, I64, P, P, P, P]),
         "gbp_terrain_move_shift_ms": (I, [P, P]),
         "gbp_coord_shift": (I, [P, P, I, ctypes.c_double, P]),
+        "gbp_terrain_derive_slopes_dev": (I, [P, P, I, P]),
+        "gbp_terrain_derive_slopes_host": (I, [P, P, I]),
+        "gbp_terrain_read_slopes_host": (I, [P, P, P, P, P]),
         "gbp_terrain_set_option": (I, [P, I, I64]),
         "gbp_terrain_get_option": (I, [P, I, P]),
         "gbp_validate_lds_plan": (I, [I, I, I64, I64, SZ, P, P, P]),

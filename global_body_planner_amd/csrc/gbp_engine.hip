@@ -1469,6 +1469,11 @@ int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value) {
     case GBP_OPT_NAN_TESTS:
       t->opt_nan_tests = value ? 1 : 0;
       return GBP_OK;
+    case GBP_OPT_DERIVE_SLOPES:  // 0, or 1 | flags on a handle that has layers
+      if (value && (!(value & 1) || (value & ~(int64_t)(1 | GBP_SLOPES_F32)) || !t->d_dx))
+        return GBP_E_INVALID_ARG;
+      t->opt_derive = value;
+      return GBP_OK;
     case GBP_OPT_FRAGILE_EPS:  // in 1e-15 units; never below the default margin
       if (value < 1000 || value > 1000000000000000LL) return GBP_E_INVALID_ARG;
       t->fragile_eps = (double)value * 1e-15;
@@ -1494,6 +1499,7 @@ int gbp_terrain_get_option(const gbp_terrain *t, int key, int64_t *value) {
     case GBP_OPT_NN_STATS: *value = t->opt_nn_stats; return GBP_OK;
     case GBP_OPT_NAN_FREE: *value = nan_free_now(t) ? 1 : 0; return GBP_OK;
     case GBP_OPT_NAN_TESTS: *value = t->opt_nan_tests; return GBP_OK;
+    case GBP_OPT_DERIVE_SLOPES: *value = t->opt_derive; return GBP_OK;
     case GBP_OPT_FRAGILE_EPS: *value = (int64_t)std::llround(t->fragile_eps * 1e15); return GBP_OK;
     case GBP_OPT_COORD_MODE:  // what the validate kernel of the current options uses
       *value = validate_coord_mode(t, t->opt_kernel == GBP_KERNEL_DIRECT);

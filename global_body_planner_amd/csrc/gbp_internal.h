@@ -12,7 +12,8 @@
 // whole cells and its host mirror;
 // gbp_replan.hip: RRT*'s kept connections carried between searches and the
 // joined path of two device trees;
-// gbp_informed.hip: the handle's informed-sampling ellipse and its sampler): the handles, the block sizes, the device
+// gbp_informed.hip: the handle's informed-sampling ellipse and its sampler;
+// gbp_slopes.hip: a handle's slope layers derived from its heights): the handles, the block sizes, the device
 // buffers' carve lists, and a tree's allocations and copies.
 // Not part of the C ABI.
 #pragma once
@@ -90,6 +91,7 @@ struct gbp_terrain {
   };
   std::vector<PendingPatch> pending;
   float last_shift_ms = -1.0f;      // device time of the last move's shift launch (-1: none)
+  int64_t opt_derive = 0;           // GBP_OPT_DERIVE_SLOPES: 0 off, else 1 | flags
 };
 
 // brings t->host up to date with the device (gbp_terrain.hip): waits for the
@@ -512,6 +514,18 @@ inline bool coords_ascending(const double *d, int n) {
 // mirror's x / y.  All or nothing: on failure (GBP_E_ALLOC, GBP_E_HIP) the
 // handle is as it was.
 GBP_INTERNAL int gbp_internal_set_geometry(gbp_terrain *t, const double *x, const double *y);
+
+// The derive launch alone, on st (gbp_slopes.hip), for gbp_terrain.hip's
+// upkeep under GBP_OPT_DERIVE_SLOPES: the nodes of `launch` (inside the map)
+// that lie in `inner` get the rule of gbp_slopes.h, the others (0, 0, 1).
+// Heights from the x-pairs zp, coordinates from the device vectors x / y,
+// results into lay[3]: the handle's own buffers or a move's second set.
+// status: null, or an update's check word (1 = write nothing).
+GBP_INTERNAL int gbp_internal_derive_slopes(const gbp_terrain *t, const void *zp, const double *x,
+                                            const double *y, double *const lay[3],
+                                            const gbp_patch::Rect &launch,
+                                            const gbp_patch::Rect &inner, int flags,
+                                            const int32_t *status, hipStream_t st);
 
 // the device's look-ahead stream of the planner loop (created once per
 // process and device; null on failure); gbp_plan.hip

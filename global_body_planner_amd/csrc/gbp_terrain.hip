@@ -376,6 +376,42 @@ int stage_patch(gbp_terrain *t, const Dest &D, const gbp_patch::Rect &q, int src
 
 constexpr size_t MAX_PENDING = 64;  // caller streams with updates the mirror has not taken in
 
+// GBP_OPT_DERIVE_SLOPES after an update of q that was given no layers: a node's
+// slope cells depend on its four neighbours' heights, so q and the nodes next
+// to it are derived again (gbp_slopes.hip), on st behind the apply launch
+int derive_around(gbp_terrain *t, const gbp_patch::Rect &q, const int32_t *status, hipStream_t st) {
+  gbp_patch::Rect d;
+  d.ix0 = std::max(q.ix0 - 1, 0);
+  d.iy0 = std::max(q.iy0 - 1, 0);
+  d.nx = std::min(q.ix0 + q.nx + 1, t->nx) - d.ix0;
+  d.ny = std::min(q.iy0 + q.ny + 1, t->ny) - d.iy0;
+  double *const lay[3] = {t->d_dx, t->d_dy, t->d_dz};
+  return gbp_internal_derive_slopes(t, t->d_z, t->d_x, t->d_y, lay, d, d,
+                                    (int)(t->opt_derive & GBP_SLOPES_F32), status, st);
+}
+
+// what gbp_terrain_update_dev leaves for the mirror
+int note_pending(gbp_terrain *t, const gbp_patch::Rect &q, hipStream_t st) {
+  int rc;
+  // the mirror takes the rectangle in lazily (host_mirror), a rejected one too:
+  // its heights are as they were, reading them again changes nothing
+  for (auto &u : t->pending)
+    if (u.stream == st) {
+      HIPCHK(hipEventRecord(u.done, st));  // behind the stream's earlier updates as well
+      u.rect = gbp_patch::rect_union(u.rect, q);
+      return GBP_OK;
+    }
+  if (t->pending.size() >= MAX_PENDING && (rc = gbp_internal_mirror_sync(t))) return rc;
+  hipEvent_t ev;
+  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  if (hipEventRecord(ev, st) != hipSuccess) {
+    (void)hipEventDestroy(ev);
+    return GBP_E_HIP;
+  }
+  t->pending.push_back({st, q, ev});
+  return GBP_OK;
+}
+
 }  // namespace
 
 __attribute__((visibility("hidden"))) int gbp_internal_mirror_sync(gbp_terrain *t) {
@@ -418,23 +454,12 @@ int gbp_terrain_update_dev(gbp_terrain *t, const gbp_rect *r, int src_layout, in
   if ((rc = launch_patch(t, dest_of(t), q, src_layout, ld, 0, z, dx, dy, dz,
                          need_check ? status : nullptr, st)))
     return rc;
-  // the mirror takes the rectangle in lazily (host_mirror), a rejected one too:
-  // its heights are as they were, reading them again changes nothing
-  for (auto &u : t->pending)
-    if (u.stream == st) {
-      HIPCHK(hipEventRecord(u.done, st));  // behind the stream's earlier updates as well
-      u.rect = gbp_patch::rect_union(u.rect, q);
-      return GBP_OK;
-    }
-  if (t->pending.size() >= MAX_PENDING && (rc = gbp_internal_mirror_sync(t))) return rc;
-  hipEvent_t ev;
-  HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  if (hipEventRecord(ev, st) != hipSuccess) {
-    (void)hipEventDestroy(ev);
-    return GBP_E_HIP;
-  }
-  t->pending.push_back({st, q, ev});
-  return GBP_OK;
+  // GBP_OPT_DERIVE_SLOPES: behind the apply launch on the same stream (a launch
+  // error is reported once the mirror knows of the rectangle)
+  int drc = GBP_OK;
+  if (t->opt_derive && !dx) drc = derive_around(t, q, need_check ? status : nullptr, st);
+  rc = note_pending(t, q, st);
+  return rc ? rc : drc;
 }
 
 int gbp_terrain_update_host(gbp_terrain *t, const gbp_rect *r, int src_layout, int64_t ld,
@@ -450,11 +475,15 @@ int gbp_terrain_update_host(gbp_terrain *t, const gbp_rect *r, int src_layout, i
   if ((rc = wait_pending(t))) return rc;
   DevBuf buf;
   if ((rc = stage_patch(t, dest_of(t), q, src_layout, ld, z, dx, dy, dz, buf, st))) return rc;
+  // GBP_OPT_DERIVE_SLOPES.  The heights are on their way by now: should this
+  // launch fail, the host copy still takes them in, and the error is returned
+  // with the layers as they were
+  const int drc = t->opt_derive && !dx ? derive_around(t, q, nullptr, st) : GBP_OK;
   HIPCHK(hipStreamSynchronize(st));
   gbp_patch::scatter(t->host.z.data(), t->nx, t->ny, q, src_layout, ld, z,
                      t->storage == GBP_STORAGE_F32);
   t->nan_free = gbp_patch::nan_free_after(t->host.z.data(), t->nx, t->ny, q, t->nan_free != 0);
-  return GBP_OK;
+  return drc;
 }
 
 int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *x, const double *y,
@@ -485,6 +514,10 @@ int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *
   // behind every earlier gbp_terrain_update_dev, whose rectangles the mirror takes in first
   if ((rc = gbp_internal_mirror_sync(t))) return rc;
   const bool moved = sx != 0 || sy != 0;
+  // GBP_OPT_DERIVE_SLOPES and no layers given: the second set's layers are
+  // derived whole from the moved heights and the new coordinates, not shifted
+  // and patched (one launch, no seam cases; tools/slopes_ab.py (d) has its cost)
+  const bool derive = t->opt_derive && !dx && t->d_dx;
   // the second set of buffers, freed at scope exit unless the swap took them
   struct Spare {
     Dest d;
@@ -494,7 +527,7 @@ int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *
         if (p) (void)hipFree(p);
     }
   } spare;
-  DevBuf staged[2];
+  DevBuf staged[2], coords;
   // device events around the shift launch alone (gbp_terrain_move_shift_ms)
   struct Timer {
     hipEvent_t e[2] = {nullptr, nullptr};
@@ -504,9 +537,9 @@ int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *
     }
   } timer;
   bool timed = false;
-  if (moved) {
+  if (moved || derive) {
     const size_t cells = (size_t)NX * NY, esz = f32 ? sizeof(float) : sizeof(double);
-    if (hipMalloc(&spare.d.zp, 2 * ((size_t)NX - 1) * NY * esz) != hipSuccess) {
+    if (moved && hipMalloc(&spare.d.zp, 2 * ((size_t)NX - 1) * NY * esz) != hipSuccess) {
       spare.d.zp = nullptr;
       return GBP_E_ALLOC;
     }
@@ -515,7 +548,9 @@ int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *
         spare.d.lay[k] = nullptr;
         return GBP_E_ALLOC;
       }
-    if (m.overlap.nx > 0 || t->d_dx) {  // no overlap and no layers: the strip is the whole map
+    const bool shift_layers = t->d_dx && !derive;
+    // no overlap and no layers to shift: the strip is the whole map
+    if (moved && (m.overlap.nx > 0 || shift_layers)) {
       ShiftArgs A;
       A.zo = t->d_z;
       A.zn = spare.d.zp;
@@ -531,7 +566,7 @@ int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *
       A.sy = m.overlap.nx > 0 ? (int)sy : NY;
       const dim3 grid((unsigned)((NY + PATCH_BLOCK - 1) / PATCH_BLOCK),
                       (unsigned)std::min(std::max((NX + SHIFT_ROWS - 1) / SHIFT_ROWS, 1), 4096),
-                      t->d_dx ? 4u : 1u);
+                      shift_layers ? 4u : 1u);
       timed = hipEventCreate(&timer.e[0]) == hipSuccess && hipEventCreate(&timer.e[1]) == hipSuccess &&
               hipEventRecord(timer.e[0], st) == hipSuccess;
       if (f32)
@@ -551,17 +586,35 @@ int gbp_terrain_move_host(gbp_terrain *t, int64_t sx, int64_t sy, const double *
         return rc;
       }
     }
+    if (derive) {  // behind the shift and the strips, with the new coordinates
+      double *cx = nullptr, *cy = nullptr;
+      rc = stage_buf(coords, [&](Stage &S) {
+        S.take(cx, (size_t)NX);
+        S.take(cy, (size_t)NY);
+      });
+      if (!rc) rc = h2d(cx, x, (size_t)NX, st);
+      if (!rc) rc = h2d(cy, y, (size_t)NY, st);
+      if (!rc)
+        rc = gbp_internal_derive_slopes(t, moved ? spare.d.zp : t->d_z, cx, cy, spare.d.lay, whole,
+                                        whole, (int)(t->opt_derive & GBP_SLOPES_F32), nullptr, st);
+      if (rc) {
+        (void)hipStreamSynchronize(st);  // nothing in flight when the buffers go
+        return rc;
+      }
+    }
     HIPCHK(hipStreamSynchronize(st));
   }
   float shift_ms = -1.0f;
   if (timed && hipEventElapsedTime(&shift_ms, timer.e[0], timer.e[1]) != hipSuccess) shift_ms = -1.0f;
   // the last step that can fail; the rest is the swap and host fields
   if ((rc = gbp_internal_set_geometry(t, x, y))) return rc;
-  if (moved) {
-    std::swap(t->d_z, spare.d.zp);  // the old buffers leave with `spare`
+  if ((moved || derive) && t->d_dx) {
     std::swap(t->d_dx, spare.d.lay[0]);
     std::swap(t->d_dy, spare.d.lay[1]);
     std::swap(t->d_dz, spare.d.lay[2]);
+  }
+  if (moved) {
+    std::swap(t->d_z, spare.d.zp);  // the old buffers leave with `spare`
     double *mz = t->host.z.data();
     gbp_patch::shift_mirror(mz, NX, NY, sx, sy, m);
     for (int k = 0; k < m.nstrips; k++)

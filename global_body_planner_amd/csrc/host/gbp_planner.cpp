@@ -159,7 +159,8 @@ FastTerrainMap FastTerrainMap::borrow(gbp_terrain *handle) {
 }
 
 FastTerrainMap::FastTerrainMap(FastTerrainMap &&o) noexcept
-    : device_(o.device_), handle_(o.handle_), owned_(o.owned_), slopes_(o.slopes_), x_size_(o.x_size_),
+    : device_(o.device_), handle_(o.handle_), owned_(o.owned_), slopes_(o.slopes_), layers_(o.layers_),
+      derive_(o.derive_), derive_f32_(o.derive_f32_), x_size_(o.x_size_),
       y_size_(o.y_size_), x_data_(std::move(o.x_data_)), y_data_(std::move(o.y_data_)) {
   o.handle_ = nullptr;
 }
@@ -203,14 +204,54 @@ void FastTerrainMap::loadDataFlat(int x_size, int y_size, const double *x, const
   gbp_terrain *h = nullptr;
   chk(gbp_terrain_create(device_, x_size, y_size, x, y, z, dx, dy, dz, GBP_STORAGE_AUTO, &h),
       "gbp_terrain_create");
+  if (derive_) {  // before the old handle goes: a failure leaves the map as it was
+    const int flags = derive_f32_ ? GBP_SLOPES_F32 : 0;
+    int rc = dx ? GBP_OK : gbp_terrain_derive_slopes_host(h, nullptr, flags);
+    if (!rc) rc = gbp_terrain_set_option(h, GBP_OPT_DERIVE_SLOPES, 1 | flags);
+    if (rc) {
+      gbp_terrain_destroy(h);
+      chk(rc, "gbp_terrain_derive_slopes_host");
+    }
+  }
   if (handle_ && owned_) gbp_terrain_destroy(handle_);
   handle_ = h;
   owned_ = true;
   slopes_ = dx != nullptr;
+  layers_ = slopes_ || derive_;
   x_size_ = x_size;
   y_size_ = y_size;
   x_data_.assign(x, x + x_size);
   y_data_.assign(y, y + y_size);
+}
+
+void FastTerrainMap::deriveSlopes(bool round_f32) {
+  chk(gbp_terrain_derive_slopes_host(handle_, nullptr, round_f32 ? GBP_SLOPES_F32 : 0),
+      "gbp_terrain_derive_slopes_host");
+  layers_ = true;
+}
+
+void FastTerrainMap::setDeriveSlopes(bool on, bool round_f32) {
+  // a borrowed handle's layers and options are its owner's
+  if (handle_ && !owned_) chk(GBP_E_UNSUPPORTED, "setDeriveSlopes on a borrowed handle");
+  if (handle_) {
+    if (on && !layers_) deriveSlopes(round_f32);
+    if (layers_)
+      chk(gbp_terrain_set_option(handle_, GBP_OPT_DERIVE_SLOPES,
+                                 on ? 1 | (round_f32 ? GBP_SLOPES_F32 : 0) : 0),
+          "gbp_terrain_set_option");
+  }
+  derive_ = on;
+  derive_f32_ = round_f32;
+}
+
+void FastTerrainMap::readSlopes(std::vector<double> &dx, std::vector<double> &dy,
+                                std::vector<double> &dz) {
+  const size_t cells = (size_t)x_size_ * y_size_;
+  dx.resize(cells);
+  dy.resize(cells);
+  dz.resize(cells);
+  chk(gbp_terrain_read_slopes_host(handle_, nullptr, dx.data(), dy.data(), dz.data()),
+      "gbp_terrain_read_slopes_host");
 }
 
 void FastTerrainMap::updateDataFlat(int ix0, int iy0, int pnx, int pny, const double *z,

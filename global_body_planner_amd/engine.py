@@ -201,6 +201,38 @@ class Terrain:
               "read")
         return out
 
+    # ---- slope layers derived from the heights ------------------------------------
+    def derive_slopes(self, rect=None, round_f32=False, stream=None):
+        """Recompute the slope layers of rect = (ix0, iy0, nx, ny), the whole
+        map when None, from the heights the handle holds
+        (gbp_terrain_derive_slopes_*, the rule of csrc/gbp_slopes.h).
+        round_f32 rounds each component through float last (SLOPES_F32).
+
+        stream None: the synchronous host entry; a handle created without
+        layers gets them, (0, 0, 1) outside rect.  A torch stream (or a raw
+        stream pointer) selects the device entry, which only enqueues there
+        and needs a handle that has layers.
+
+        To keep the layers derived across update / move calls that bring no
+        layers: set_option(OPT_DERIVE_SLOPES, 1 | flags)."""
+        r = None if rect is None else L.Rect(*[int(v) for v in rect])
+        rp = None if r is None else ctypes.byref(r)
+        flags = L.SLOPES_F32 if round_f32 else 0
+        if stream is None:
+            check(self._lib.gbp_terrain_derive_slopes_host(self._h, rp, flags), "derive_slopes")
+        else:
+            sp = _VP(stream.cuda_stream) if hasattr(stream, "cuda_stream") else _VP(int(stream))
+            check(self._lib.gbp_terrain_derive_slopes_dev(self._h, rp, flags, sp), "derive_slopes")
+
+    def read_slopes(self, rect=None):
+        """The slope layers the device holds (gbp_terrain_read_slopes_host):
+        (dx, dy, dz), each float64 [nx][ny] of rect, the whole map when None."""
+        r = L.Rect(0, 0, self.nx, self.ny) if rect is None else L.Rect(*[int(v) for v in rect])
+        out = [np.empty((max(r.nx, 0), max(r.ny, 0)), np.float64) for _ in range(3)]
+        check(self._lib.gbp_terrain_read_slopes_host(self._h, ctypes.byref(r),
+                                                     *[_np_ptr(v) for v in out]), "read_slopes")
+        return tuple(out)
+
     # ---- helpers --------------------------------------------------------------
     def _dev(self, t, dtype, shape_tail=None, name="tensor"):
         if not isinstance(t, torch.Tensor):

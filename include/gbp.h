@@ -145,7 +145,8 @@ typedef struct gbp_rect { int32_t ix0, iy0, nx, ny; } gbp_rect; /* cells [ix0, i
                                   cells are taken */
 /* z, and dx / dy / dz (all three or none), in src_layout with leading dimension
  * ld.  Slope layers given for a handle created without them: GBP_E_INVALID_ARG;
- * omitted for a handle that has them: they stay as they are.  A rectangle that
+ * omitted for a handle that has them: they stay as they are (or are derived
+ * again from the heights: GBP_OPT_DERIVE_SLOPES, below).  A rectangle that
  * is empty or leaves the map, or an ld below the layout's minimum: GBP_E_SHAPE;
  * an unknown layout: GBP_E_INVALID_ARG.
  * All or nothing: an fp32-storage handle holds only heights that round-trip
@@ -204,7 +205,8 @@ int gbp_terrain_read_host(gbp_terrain *t, const gbp_rect *r, int copy, double *z
  * Slope layers given to a handle created without them: GBP_E_INVALID_ARG.
  * Omitted for a handle that has them: the overlap's slope values shift with the
  * heights and the strips' slope cells become (0, 0, 1), what a create without
- * layers reads everywhere.
+ * layers reads everywhere (with GBP_OPT_DERIVE_SLOPES on: the layers of the
+ * moved map are derived whole from its heights and the new coordinates).
  * All or nothing: descending coordinates or a NaN among them:
  * GBP_E_INVALID_ARG; an ld below the layout's minimum: GBP_E_SHAPE; an
  * fp32-storage handle and a strip height that is neither NaN nor
@@ -237,6 +239,47 @@ int gbp_terrain_move_shift_ms(const gbp_terrain *t, float *ms);
  * untouched: a changed spacing, a displacement by a fraction of a cell, n < 2,
  * NaN.  FastTerrainMap::moveFromGridMap calls it with rel_tol = 1.0 / 1024. */
 int gbp_coord_shift(const double *old_c, const double *new_c, int n, double rel_tol, int *shift);
+
+/* ---- a terrain's slope layers derived from its heights ----------------------
+ * The maps a node receives from a sensor pipeline carry an elevation layer and
+ * no slope layers.  These entries compute dx / dy / dz on the device from the
+ * heights the handle holds (csrc/gbp_slopes.h, the recipe of
+ * terrain_data.synth_fractal).  For node (ix, iy) and each axis (x shown, m =
+ * ix - 1, p = ix + 1; a neighbour is usable when it lies in the map and its
+ * height is not NaN):
+ *   both usable   g = (z_p - z_m) / (x_p - x_m)
+ *   only p        g = (z_p - z_c) / (x_p - x_c)
+ *   only m        g = (z_c - z_m) / (x_c - x_m)
+ *   neither       g = 0.0
+ * then l = sqrt((gx*gx + gy*gy) + 1.0) and (dx, dy, dz) = ((-gx)/l, (-gy)/l,
+ * 1.0/l).  A node whose own height is NaN gets (0, 0, 1).  Heights are read as
+ * the handle stores them (fp32 storage widened to double).  With
+ * GBP_SLOPES_F32 each component is rounded through float last, what a grid_map
+ * layer would hold.  Any other flag bit: GBP_E_INVALID_ARG. */
+#define GBP_SLOPES_F32 2
+/* Recomputes the slope cells of the nodes in r (NULL: the whole map); reads one
+ * node beyond r on each side where the map has one.  Ordered on `stream` like
+ * gbp_terrain_update_dev; it only enqueues and cannot allocate, so a handle
+ * without slope layers is GBP_E_INVALID_ARG.  Rectangle errors as
+ * gbp_terrain_update_*.  The heights do not change, so the call leaves nothing
+ * for the host copy and is NOT among the device updates that the _host entries
+ * wait for: before gbp_terrain_read_slopes_host, gbp_terrain_derive_slopes_host
+ * or any other _host entry that reads or writes the layers, the caller
+ * synchronises `stream` (ordering against other streams is the caller's, as
+ * for every _dev entry). */
+int gbp_terrain_derive_slopes_dev(gbp_terrain *t, const gbp_rect *r, int flags, gbp_stream stream);
+/* The same on the handle's host stream behind every earlier
+ * gbp_terrain_update_dev, synchronous.  A handle created without slope layers
+ * gets them here: (0, 0, 1) outside r, derived inside.  If it fails at any
+ * point the handle is as it was. */
+int gbp_terrain_derive_slopes_host(gbp_terrain *t, const gbp_rect *r, int flags);
+/* The slope layers the device holds, each x-major [r.nx][r.ny] (host,
+ * synchronous, after every earlier gbp_terrain_update_dev and the derive launch
+ * it enqueued under GBP_OPT_DERIVE_SLOPES; not after a
+ * gbp_terrain_derive_slopes_dev, see there): the counterpart of
+ * gbp_terrain_read_host.  A handle without layers: GBP_E_INVALID_ARG. */
+int gbp_terrain_read_slopes_host(gbp_terrain *t, const gbp_rect *r, double *dx, double *dy,
+                                 double *dz);
 
 /* engine options (per handle) */
 #define GBP_OPT_KERNEL        1  /* GBP_KERNEL_* for the validate/extend entry points */
@@ -288,6 +331,23 @@ int gbp_coord_shift(const double *old_c, const double *new_c, int n, double rel_
                                     gbp_terrain_read_host)                             */
 #define GBP_OPT_NAN_TESTS    22  /* 1: always run the general state check, whatever
                                     GBP_OPT_NAN_FREE reads (A/B runs, tests); default 0 */
+#define GBP_OPT_DERIVE_SLOPES 23 /* 0 (default): off.  1 | flags (flags: GBP_SLOPES_F32):
+                                    gbp_terrain_update_dev / _update_host / _move_host
+                                    calls given NO slope layers keep the layers derived
+                                    from the heights.  An update re-derives its
+                                    rectangle and the nodes next to it (update_dev on
+                                    the same stream behind its apply launch, skipped
+                                    with a rejected patch); after a move the layers are
+                                    those of a whole-map derivation of the moved map
+                                    with its new coordinates.  Calls given layers write
+                                    them as before.  Should the derive launch of a
+                                    gbp_terrain_update_host itself fail (a HIP launch
+                                    error), the call returns that error with the
+                                    heights updated on the device and in the host copy
+                                    and the layers of the rectangle as they were.
+                                    Setting it launches nothing; a
+                                    handle without slope layers: GBP_E_INVALID_ARG (run
+                                    gbp_terrain_derive_slopes_host first)              */
 #define GBP_KERNEL_DIRECT     0  /* one lane per attempt                              */
 #define GBP_KERNEL_PERSISTENT 1  /* persistent waves, lanes re-packed per sample      */
 int gbp_terrain_set_option(gbp_terrain *t, int key, int64_t value);

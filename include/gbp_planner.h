@@ -178,6 +178,26 @@ class FastTerrainMap {
   template <class GridMap>
   bool moveFromGridMap(const GridMap &map);
 
+  // Slope layers derived on the device from the heights the handle holds
+  // (gbp_terrain_derive_slopes_host, the rule of gbp.h: central differences,
+  // (-gx, -gy, 1) / |.|, one-sided beside the map's edge and beside NaN),
+  // for sources that carry an elevation layer and no dx / dy / dz.
+  // deriveSlopes derives the whole map now; round_f32 rounds each component
+  // through float, what a grid_map layer would hold.
+  void deriveSlopes(bool round_f32 = true);
+  // Off by default.  While on, loadData*, loadDataFromGridMap, updateData*,
+  // updateFromGridMap, moveDataFlat and moveFromGridMap take the source's
+  // layers when it has them, as always, and derive the layers when it has none,
+  // instead of leaving (0, 0, 1) or stale values (GBP_OPT_DERIVE_SLOPES on the
+  // handle: an update re-derives its rectangle and the nodes next to it, a
+  // move the whole map).  Turning it on for a loaded map without layers
+  // derives them now.  The setting survives a reload into a new handle.  On a
+  // map made by borrow() it throws EngineError(GBP_E_UNSUPPORTED): the handle's
+  // layers and options are its owner's (gbp_terrain_set_option there).
+  void setDeriveSlopes(bool on, bool round_f32 = true);
+  // the layers the device holds, flat x-major [x_size * y_size] each
+  void readSlopes(std::vector<double> &dx, std::vector<double> &dy, std::vector<double> &dz);
+
   double getGroundHeight(const double x, const double y);               // :94-132
   bool heightIsNan(const double x, const double y);                     // :135-157
   std::array<double, 3> getSurfaceNormal(const double x, const double y);  // :160-213
@@ -196,6 +216,8 @@ class FastTerrainMap {
   gbp_terrain *handle_ = nullptr;
   bool owned_ = true;
   bool slopes_ = false;  // the handle was loaded with slope layers
+  bool layers_ = false;  // it holds slope layers: loaded, or derived since
+  bool derive_ = false, derive_f32_ = true;  // setDeriveSlopes
   int x_size_ = 0, y_size_ = 0;
   std::vector<double> x_data_, y_data_;
 };
